@@ -14,7 +14,9 @@ One step = one batch of message headers through ring lookup + directory probe
          moves headers to their owner, which probes and buckets them.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md for the byte model behind the
-roofline object).
+roofline object).  A plain run sets up, warms up, times --steps steps and prints
+the line; --full adds the per-kernel events and rooflines, the secondary configs
+and the CPU baselines; --dump-outputs DIR writes the last timed step's results.
 """
 import argparse
 import contextlib
@@ -322,9 +324,9 @@ def setup_workload(args, workload, world, rank, local, dev, tcd, msgs, grains):
             del ks
     torch.cuda.synchronize()
     owner_share = float(counts.max().item()) / G_total
-    # the same share under the other silo set (generation 1 literal vs balanced), from a sample
-    by_set = {}
-    for name, ss in SILO_SETS.items():
+    # the same share under the other silo set (generation 1 literal vs balanced), from a sample (--full)
+    by_set = {} if args.full else None
+    for name, ss in SILO_SETS.items() if args.full else ():
         sp, so = g.ring_build(args.mode, ss)
         e2 = g.GrainDispatch(device=local, table_capacity=1024)
         e2.ring_set(args.mode, sp, so)
@@ -454,6 +456,33 @@ def timed_steps(router, keys, n_act, stream, steps, warmup, settle=SETTLE_STEPS,
     t = torch.tensor([wall], dtype=torch.float64)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item()), ev0.elapsed_time(ev1), res
+
+
+DUMP_SAMPLE = 1 << 20          # elements written of a larger output array
+DUMP_BUDGET = 60 << 20         # bytes one rank writes for one --dump-outputs
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0, world: int = 1):
+    """--dump-outputs: the arrays {name: 1-D torch tensor or numpy array, None skipped} the last timed step
+    returned, as DIR/<name>.npy (DIR/<name>.rank<r>.npy at N > 1) in float64 -- every value is an
+    integer below 2^32, so the files are exact (int32 tensors hold uint32 bit patterns and are written as
+    such).  An array over the sample size is written as its elements at that many sorted positions drawn
+    from a generator seeded by the array's length alone: two runs, or two builds, with the same arguments
+    write the same positions of the same inputs' results."""
+    arrays = {k: v for k, v in arrays.items() if v is not None}
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_SAMPLE, DUMP_BUDGET // (8 * max(1, len(arrays))))
+    for name, a in arrays.items():
+        n = int(a.shape[0])
+        if n > cap:
+            idx = np.sort(np.random.default_rng(0x5EED0D00 + n).integers(0, n, size=cap, dtype=np.int64))
+            a = a[torch.from_numpy(idx).to(a.device)] if isinstance(a, torch.Tensor) else a[idx]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        if a.dtype == np.int32:
+            a = a.view(np.uint32)
+        suffix = "" if world == 1 else f".rank{rank}"
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.astype(np.float64))
 
 
 T_START = time.perf_counter()
@@ -598,12 +627,14 @@ def compact_line(full: dict, full_path=None) -> dict:
 
 
 def emit(full: dict, args):
-    """Writes the full record to --full-out, prints the compact line (one JSON line, <= LINE_CAP bytes)."""
+    """Writes the full record to --full-out (if any), prints the compact line (one JSON line, <= LINE_CAP
+    bytes)."""
     path = args.full_out
     try:
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        with open(path, "w") as f:
-            json.dump(full, f, indent=1)
+        if path:
+            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+            with open(path, "w") as f:
+                json.dump(full, f, indent=1)
     except OSError as ex:
         print(f"bench: full record not written: {ex!r}", file=sys.stderr, flush=True)
         path = None
@@ -644,8 +675,18 @@ def main():
     ap.add_argument("--no-target", action="store_true", help="cfg4: do not write the target node per message")
     ap.add_argument("--rehearse-one-gpu", action="store_true",
                     help="rehearsal only: every rank on cuda:0, gloo, host-staged all-to-all")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "gpurun_out", "bench_full.json"),
-                    help="where the full record (every kernel table) is written; the printed line is its summary")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: per-kernel events and rooflines, the secondary "
+                         "configs (cfg 3, cfg 4, churn, mixed directory, host path, cfg 5 latency, cfg 1 shape), the "
+                         "other silo set and the CPU baselines, each still under its own switch (--no-secondary, "
+                         "--no-cpu-baseline, --profile-steps, --latency-batches).  Without it a run sets up, warms "
+                         "up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float64; arrays over 2^20 elements as a fixed seeded sample of 2^20)")
+    ap.add_argument("--full-out", default=None,
+                    help="where the full record (every kernel table) is written; the printed line is its summary "
+                         "(default with --full: bench_out/bench_full.json; without --full: not written)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="a handle option for every handle (graindispatch.OPTIONS: GD_OPT_*), e.g. bucket=2")
     ap.add_argument("--pipeline", action="store_true",
@@ -658,6 +699,14 @@ def main():
                          "(settle steps, then gd_tune_agree across ranks at N > 1; the exchange pipeline runs "
                          "unoverlapped while it times, DESIGN 10)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        # the plain run: set up, warm up, time the steps, print the line
+        args.no_secondary = args.no_cpu_baseline = True
+        args.profile_steps = args.latency_batches = 0
+    elif args.full_out is None:
+        args.full_out = os.path.join(ROOT, "bench_out", "bench_full.json")
     for kv in args.opt:
         k, v = kv.split("=", 1)
         g.DEFAULT_OPTIONS[k] = int(v)
@@ -698,6 +747,9 @@ def main():
     wall_max, gpu_ms, res = timed_steps(router, keys, n_act, stream, args.steps, args.warmup, settle_steps(args),
                                         w["agree"])
     value = N * args.steps * world / wall_max
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {k: getattr(res, k) for k in ("status", "silo", "act", "perm", "offsets",
+                                                                     "recv_idx", "recv_src")}, rank, world)
     secondary = {}
     if world > 1 and args.workload == "cfg2" and not args.no_secondary:
         # BASELINE cfg 3 is the node-level configuration: 64M Zipf(1.1) messages over 100M grains
@@ -747,7 +799,7 @@ def main():
     st_ok = int((res.status == 0).sum().item())
 
     # ---- per-kernel durations (separate steps, HIP events around every launch) -----
-    acts_np = res.act.cpu().numpy().view(np.uint32)
+    acts_np = res.act.cpu().numpy().view(np.uint32) if args.profile_steps > 0 else None
     kt = profile_kernels(e, router, keys, n_act, stream, args.profile_steps)
     kernels, roofline = roofline_of(kt, max(1, args.profile_steps), m_recv, n_act, acts_np, args.workload, world)
     # the library exchange's RCCL rounds on every rank (HIP events around each grouped round, the
@@ -1429,14 +1481,14 @@ def hop_form(e, m: int, n_act: int) -> str:
 def run_cfg4(args, world, rank, local, dev):
     """--workload cfg4: the cascade line (measure_cfg4) printed on rank 0."""
     line = measure_cfg4(args, world, rank, local, dev, args.steps, args.warmup, args.profile_steps,
-                        with_cpu=not args.no_cpu_baseline)
+                        with_cpu=not args.no_cpu_baseline, dump=args.dump_outputs)
     if rank == 0:
         line["bench_wall_s"] = round(time.perf_counter() - T_START, 1)
         emit(line, args)
     dist.destroy_process_group()
 
 
-def measure_cfg4(args, world, rank, local, dev, steps, warmup, profile_steps, with_cpu):
+def measure_cfg4(args, world, rank, local, dev, steps, warmup, profile_steps, with_cpu, dump=None):
     """One step = one whole cascade: `--hops` publish rounds from `--seeds` publishers, each round =
     expand the frontier's follower lists (ChirperAccount.cs:131-134) -> route every NewChirp (ring
     owner + directory probe) -> bucket per activation -> next frontier.  Value = messages routed
@@ -1526,6 +1578,10 @@ def measure_cfg4(args, world, rank, local, dev, steps, warmup, profile_steps, wi
     wall_max, msgs_total = float(tw[0]), float(ts[1])
     hop_msgs = [h.messages for h in hops]
     hop_front = [h.n_frontier if hasattr(h, "n_frontier") else int(h.frontier.shape[0]) for h in hops]
+    if dump:
+        # the last timed cascade, every hop (gd_fanout_multi_fetch: host copies)
+        dump_outputs(dump, {f"hop{i}_{k}": v for i, f in enumerate(runner.fetch(hops)) for k, v in f.items()
+                            if isinstance(v, np.ndarray)}, rank, world)
 
     kernels, roofline = {}, None
     if profile_steps > 0:

@@ -15,7 +15,7 @@ for r in $(seq 1 "$ROUNDS"); do
     OPTS=()
     if [ "$SET" != "-" ]; then for kv in $SET; do OPTS+=(--opt "$kv"); done; fi
     OUT="$ROOT/gpurun_out/ab_${TAG}_${i}_${r}.json"
-    timeout -k 10 300 python3 "$ROOT/bench.py" $ARGS --no-cpu-baseline --latency-batches 0 --no-secondary "${OPTS[@]}" \
+    timeout -k 10 300 python3 "$ROOT/bench.py" --full $ARGS --no-cpu-baseline --latency-batches 0 --no-secondary "${OPTS[@]}" \
         > "$OUT" 2> "$OUT.err" || { echo "set $i round $r failed"; tail -5 "$OUT.err"; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); st=(d.get('roofline') or {}).get('bucketing_stage') or {}; print(sys.argv[2], 'round', sys.argv[3], round(d['value']/1e9,3), 'G/s', d['ms_per_step'], 'ms/step, stage', st.get('ms_per_step'))" "$OUT" "[$SET]" "$r"
   done

@@ -7,6 +7,6 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$ROOT/gpurun_out"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 \
-    --master-port $((29600 + N)) "$ROOT/bench.py" --gpus "$N" --rehearse-one-gpu --no-cpu-baseline \
+    --master-port $((29600 + N)) "$ROOT/bench.py" --full --gpus "$N" --rehearse-one-gpu --no-cpu-baseline \
     --full-out "$ROOT/gpurun_out/rehearse_w${N}_full.json" "$@" \
     > "$ROOT/gpurun_out/rehearse_w${N}.json" 2> "$ROOT/gpurun_out/rehearse_w${N}.err"
