@@ -207,8 +207,10 @@ int gd_dir_unregister(gd_handle* h, const gd_key* keys, const uint32_t* acts, ui
  * stream (device arrays, outputs optional): no host round trip, so a host interleaves them with
  * gd_route_bucket_device batches and the stream runs them back to back; the probe indexes are
  * re-projected for the touched slots, not rebuilt.  Same semantics as gd_dir_register_device /
- * gd_dir_unregister; a device-side failure (table full, claims not settled after the gated passes)
- * is returned by the next synchronising call on the handle (gd_synchronize, gd_stats_get, ...).
+ * gd_dir_unregister; a device-side failure (table full, a silo index above 0xFFFE: GD_EINVAL, claims
+ * not settled after the gated passes) is returned once by the next synchronising call on the handle
+ * (gd_synchronize, gd_stats_get, ...); a synchronous gd_dir_register / gd_dir_register_device that
+ * comes first returns it before doing any work of its own, and succeeds when repeated.
  * gd_dir_unregister_device with d_out_removed NULL is one launch (which of a key's matching items
  * removes it is then unobservable: the CAS on the entry's LIVE meta picks it); with a report, the
  * first matching item of the batch is elected in a second launch. */

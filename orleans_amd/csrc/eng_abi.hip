@@ -190,7 +190,7 @@ int gd_synchronize(gd_handle* h) {
 
 int gd_stats_get(gd_handle* h, gd_stats* out) {
     if (!h || !out) return set_err(h, GD_EINVAL, "null argument");
-    GD_TRY(pull_counters(h));
+    GD_TRY(sync_checked(h));               // a synchronising call: an asynchronous batch's error surfaces here
     out->routed = h->routed;
     out->table_live = h->ctr_host.live;
     out->table_tombstones = h->ctr_host.tomb;
@@ -287,7 +287,14 @@ namespace gdx {
 // end; a device error (table full, unsettled claims) surfaces at the next synchronising call.
 int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t n, gd_val* out_vals,
                   uint8_t* out_ins, bool async) {
-    GD_TRY(async ? maybe_grow_async(h, n) : maybe_grow_table(h, n));
+    if (async) {
+        GD_TRY(maybe_grow_async(h, n));
+    } else {
+        // an earlier asynchronous batch's device error is reported (and cleared) here, before this batch does
+        // any work: left pending it would stop the claim passes below at once and be taken for this batch's
+        GD_TRY(sync_checked(h));
+        GD_TRY(grow_table(h, n));
+    }
     const uint32_t op = ++h->dir_op;
     // the directory batches' own scratch (dir_scr): no bucketing left running on the bucket stream
     // shares it, so a batch need not wait for one (bfence) -- it overlaps the previous batch's bucketing
@@ -316,7 +323,8 @@ int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t 
         uint32_t* rc = (uint32_t*)h->reg_retry.p;
         GD_TRY(launch(h, "k_reg_find_take", g, b, 0, k_reg_find_take, dk, n, h->slots, mask, h->ctr, dvals,
                       table_args(h), slot_of, is_new, win, rc, rc + 1, last));
-        // a pass settles one new grain of each group colliding on a first free slot: a batch of 2^16 items
+        // the take settles one new grain of each group colliding on a first free slot, a claim pass all it runs
+        // but the items that read a claim's election word too early: a batch of 2^16 items
         // settles in 3 (cfg 2's 1 % churn batches: 222 deferred by the take, 3 by pass 1, none by pass 2),
         // and each gated launch costs ~1.4 us even when its gate is shut
         const uint32_t passes = n <= (1u << 16) ? REG_PASSES_SMALL : REG_PASSES;
@@ -351,16 +359,7 @@ int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t 
         GD_TRY(launch(h, "k_reg_report", g, b, 0, k_reg_report, (const uint32_t*)slot_of, (const uint32_t*)win, n,
                       (const Slot*)h->slots, out_vals, out_ins));
     if (async) return GD_OK;
-    GD_TRY(pull_counters(h));
-    if (h->ctr_host.err) {
-        const uint32_t e = h->ctr_host.err;
-        HIP_TRY(h, hipMemsetAsync(&h->ctr->err, 0, sizeof(uint32_t), h->stream));
-        GD_TRY(sync(h));
-        return set_err(h, (e & 2) ? GD_EFULL : (e & 4) ? GD_EINVAL : GD_ETIMEOUT,
-                       "gd_dir_register: device error bits 0x%x (2: table full, 4: silo index > 0xFFFE, "
-                       "64: an asynchronous batch's claims did not settle)", e);
-    }
-    return GD_OK;
+    return sync_checked(h);
 }
 
 // RemoveActivation (Force) for a batch of device-resident keys / activations; out_removed (device, may be

@@ -1114,20 +1114,27 @@ int pinned_scratch(gd_handle* h, size_t bytes) {
     return GD_OK;
 }
 
+// The device error bits of the last counter read-back (pull_counters) as the call's result: cleared on
+// the device, so each error is reported once.
+int report_device_error(gd_handle* h) {
+    const uint32_t e = h->ctr_host.err;
+    if (!e) return GD_OK;
+    HIP_TRY(h, hipMemsetAsync(&h->ctr->err, 0, sizeof(uint32_t), h->stream));
+    GD_TRY(sync(h));
+    if (e == ERR_CTX_RANGE)
+        return set_err(h, GD_EINVAL, "an ActivationDirectory entry's context index is not below n_ctx");
+    if (e & 2u) return set_err(h, GD_EFULL, "the directory table is full (device error bits 0x%x)", e);
+    if (e & 4u)
+        return set_err(h, GD_EINVAL, "a registration's silo index is above 0xFFFE (device error bits 0x%x)", e);
+    if (e & ERR_UNSETTLED)
+        return set_err(h, GD_ETIMEOUT, "an asynchronous registration's claims did not settle (device error bits 0x%x)", e);
+    return set_err(h, GD_EFULL, "device error bits 0x%x", e);
+}
+
 // Surface device-side error bits after a synchronising call.
 int sync_checked(gd_handle* h) {
     GD_TRY(pull_counters(h));
-    if (h->ctr_host.err) {
-        const uint32_t e = h->ctr_host.err;
-        HIP_TRY(h, hipMemsetAsync(&h->ctr->err, 0, sizeof(uint32_t), h->stream));
-        GD_TRY(sync(h));
-        if (e == ERR_CTX_RANGE)
-            return set_err(h, GD_EINVAL, "an ActivationDirectory entry's context index is not below n_ctx");
-        if (e & ERR_UNSETTLED)
-            return set_err(h, GD_ETIMEOUT, "an asynchronous registration's claims did not settle (device bits 0x%x)", e);
-        return set_err(h, GD_EFULL, "device error bits 0x%x", e);
-    }
-    return GD_OK;
+    return report_device_error(h);
 }
 
 // maybe_grow_table without the read-back while the last copy of the counters is current (no untracked
@@ -1143,6 +1150,11 @@ int maybe_grow_async(gd_handle* h, uint64_t incoming) {
 
 int maybe_grow_table(gd_handle* h, uint64_t incoming) {
     GD_TRY(pull_counters(h));
+    return grow_table(h, incoming);
+}
+
+// maybe_grow_table after a read-back of the counters (pull_counters, sync_checked) with nothing enqueued since.
+int grow_table(gd_handle* h, uint64_t incoming) {
     const unsigned long long used = h->ctr_host.live + h->ctr_host.tomb + incoming;
     if (used * 4 <= h->capacity * 3) return GD_OK;  // keep load <= 0.75
     unsigned long long cap = h->capacity;

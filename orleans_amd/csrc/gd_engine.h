@@ -357,7 +357,9 @@ int bucket_device(gd_handle* h, const uint32_t* acts, uint32_t n, uint32_t n_act
 int sync(gd_handle* h);
 int pinned_scratch(gd_handle* h, size_t bytes);
 int sync_checked(gd_handle* h);
+int report_device_error(gd_handle* h);
 int maybe_grow_table(gd_handle* h, uint64_t incoming);
+int grow_table(gd_handle* h, uint64_t incoming);
 int fwd_pack(gd_handle* h, const gd_key* keys, const uint8_t* st, const uint32_t* silo, uint32_t n, uint32_t n_shards,
              uint32_t my_rank, void* out_keys, uint32_t* out_pos, uint32_t* counts, const uint32_t* n1 = nullptr);
 bool host_pinned(const void* p);

@@ -873,12 +873,15 @@ static __global__ void __launch_bounds__(BLOCK) k_ring_hashes(const uint32_t* __
 
 // ------------------------------------------------------------------ directory maintenance
 // AddSingleActivation (GrainDirectoryPartition.cs:304-326, GrainInfo :110-124) for a batch.
-// Phase 1: find the key's slot or claim an empty one.  A lane that meets a slot
-// another lane has claimed but not yet published does NOT wait (a divergent
+// Phase 1: find the key's slot or claim a free one.  A lane that meets a slot
+// another lane has claimed in this launch reads the claimer off the slot's
+// election word and joins it (its twin) or walks on (another key); a lane that
+// loses the CAS on its free slot walks on from that slot in the same pass.  Only
+// a lane that finds the election word still zero does NOT wait (a divergent
 // wait can starve the claimer of the same wave once the compiler sinks its
 // publish to the loop exit): it is marked RETRY and the host relaunches the
 // kernel for the retried items, after the kernel boundary has published every
-// claim.  "Not yet published" is read off the meta alone (round 6): CLAIMED, or
+// claim.  "Claimed in this launch" is read off the meta alone (round 6): CLAIMED, or
 // PENDING with this launch's tag in the silo field (claim_tag) -- a PENDING slot of
 // an earlier launch has its key published by that launch's end.  So a claim needs no
 // release fence (an agent-scope release writes the XCD's L2 back, per wave) and a
@@ -930,9 +933,11 @@ static __global__ void __launch_bounds__(BLOCK) k_reg_claim(const gd_key* __rest
     claim_counters(ctr, pd, reused);
 }
 
-// k_reg_take + the gated claim passes of an asynchronous batch: a pass settles one new grain of each group
-// of new grains colliding on their first free slots (a claim hides its key from its own pass), so a
-// large batch needs several (300,000 new grains in a 2M-slot table: more than 3)
+// k_reg_take + the gated claim passes of an asynchronous batch.  k_reg_take settles one new grain of each
+// group colliding on a first free slot and defers the others; a claim pass settles every item it runs
+// except those that read a fresh claim's election word before it was written (they defer again), so the
+// passes after the first are a margin for that window, wider in a large batch (300,000 new grains in a
+// 2M-slot table have needed more than 3)
 constexpr uint32_t REG_PASSES = 12;
 constexpr uint32_t REG_PASSES_SMALL = 4;    // ... for a batch of at most 2^16 items
 // The claim pass of an asynchronous batch (gd_dir_register_device_async): pass p > 0 runs only when
@@ -1173,59 +1178,74 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
     // The key's first tombstone, reused when the chain does not hold the key (round 6: a directory under
     // continuous RemoveActivation / AddSingleActivation churn no longer fills with tombstones until a
     // rehash).  Every item of one key meets the same first free slot, and a claim is a CAS, so a key is
-    // never placed twice; a tombstone taken meanwhile defers the item to the next pass.
+    // never placed twice.  An item that loses its free slot (the tombstone, or the empty slot ending the
+    // chain) to another item of the launch walks on from that slot in the same pass: it meets the winner's
+    // claim there -- its twin's: join it; another key's: the chain's next free slot is the next try.  (Deferred
+    // to the next pass instead, k new grains of a batch sharing a chain took k passes, and an asynchronous
+    // batch has REG_PASSES_SMALL.)
     unsigned long long tomb_s = ~0ull, tomb_dist = 0;
     uint32_t tomb_meta = 0;
-    // claim slot t (its meta `expected`) for the key: the key, then PENDING with this launch's tag (read
-    // as unpublished by this launch's other items; published to later launches by the kernel boundary)
-    auto claim = [&](unsigned long long t, uint32_t expected, unsigned long long d) -> bool {
-        uint32_t* mp = &slots[t].meta;
-        if (!__hip_atomic_compare_exchange_strong(mp, &expected, make_meta(SLOT_CLAIMED, 0), __ATOMIC_RELAXED,
-                                                  __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            return false;
-        if (last) atomicMax(&last[t], ~i);                   // the claimer, readable by this launch's walks
-        Slot& sl = slots[t];
-        sl.n0 = n0;
-        sl.n1 = n1;
-        sl.tcd = tcd;
-        sl.act = NONE32;
-        __hip_atomic_store(mp, make_meta(SLOT_PENDING, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        pdist = (uint32_t)d;                                 // max_probe: claim_counters
-        return true;
-    };
-    // the chain holds no copy of the key: take its first tombstone (or report a full table)
-    auto take_tomb = [&]() {
-        if (tomb_s == ~0ull) {
-            atomicOr(&ctr->err, 2u);
-        } else if (claim(tomb_s, tomb_meta, tomb_dist)) {
-            reused = true;                                   // tomb - 1: claim_counters
-            res = (uint32_t)tomb_s;
-            fresh = 1;
-        } else {
-            res = SLOT_RETRY;
-            atomicAdd(retry, 1u);
-        }
-    };
     for (;;) {
         uint32_t* meta_p = &slots[s].meta;
         const uint32_t meta = __hip_atomic_load(meta_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const uint32_t st = slot_state(meta);
-        if (st == SLOT_EMPTY) {
-            if (tomb_s != ~0ull) {
-                take_tomb();
-                break;
-            }
-            if (claim(s, meta, dist)) {
-                res = (uint32_t)s;
-                fresh = 1;
-                break;
-            }
-            continue;   // lost the CAS: re-read the same slot
+        // the chain ends (an empty slot, or the whole table walked) without a copy of the key
+        const bool ends = st == SLOT_EMPTY || dist > mask;
+        if (ends && st != SLOT_EMPTY && tomb_s == ~0ull) {
+            atomicOr(&ctr->err, 2u);                         // no free slot: the table is full
+            break;
         }
-        if (st == SLOT_CLAIMED || (st == SLOT_PENDING && slot_silo(meta) == tag)) {
+        bool won = false;
+        const bool tomb = tomb_s != ~0ull;
+        const unsigned long long t = tomb ? tomb_s : s, d = tomb ? tomb_dist : dist;
+        if (ends) {
+            // claim slot t for the key: the claimer's index in the slot's election word (readable by this
+            // launch's walks), the key, then PENDING with this launch's tag (read as unpublished by this
+            // launch's other items; published to later launches by the kernel boundary)
+            uint32_t expected = tomb ? tomb_meta : meta;
+            uint32_t* mp = &slots[t].meta;
+            won = __hip_atomic_compare_exchange_strong(mp, &expected, make_meta(SLOT_CLAIMED, 0), __ATOMIC_RELAXED,
+                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (won) {
+                if (last) atomicMax(&last[t], ~i);
+                Slot& sl = slots[t];
+                sl.n0 = n0;
+                sl.n1 = n1;
+                sl.tcd = tcd;
+                sl.act = NONE32;
+                __hip_atomic_store(mp, make_meta(SLOT_PENDING, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        // The winner's writes above stay inside the loop: the wave's losers of the same slot read the election
+        // word in their next iteration.  Without this join the winner's block only leads out of the loop, and
+        // a divergent wave runs such a block after its last lane has left the loop -- after the losers had
+        // read a zero word and deferred, one settled item a wave and pass.  The builtin emits no instruction:
+        // it is a convergent call the compiler does not duplicate, which keeps the join one block of the
+        // loop.  That is a property of code generation, not of the memory model, and correctness does not
+        // rest on it (a loser that reads a zero word defers, as before): a compiler that moves the block out
+        // again brings back the k-passes behaviour silently, and tests/test_gpu_dir_chains.py's asynchronous
+        // cases (20 new grains on one tombstoned chain in 4 passes) then fail with GD_ETIMEOUT.
+        __builtin_amdgcn_wave_barrier();
+        if (won) {
+            pdist = (uint32_t)d;                             // max_probe: claim_counters
+            reused = tomb;                                   // tomb - 1: claim_counters
+            res = (uint32_t)t;
+            fresh = 1;
+            break;
+        }
+        if (ends) {
+            // lost slot t: walk on from it (an empty slot that was lost is read again as it is)
+            s = t;
+            dist = d;
+            tomb_s = ~0ull;
+            continue;
+        }
+        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && slot_silo(meta) == tag);
+        if (unpublished) {
             // claimed in this launch: its key is not published to this launch, but its claimer is (the slot's
             // election word, written right after the claim): the key's twin -- join it -- or another key's
-            // claim -- walk on.  Only a claim not yet recorded defers.
+            // claim -- walk on.  Only a claim whose word is not yet visible defers the item (no wait: the
+            // claimer may be a lane of this wave).
             const uint32_t w = last ? __hip_atomic_load(&last[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
             if (w == 0) {
                 res = SLOT_RETRY;
@@ -1239,7 +1259,6 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
                 break;
             }
         }
-        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && slot_silo(meta) == tag);
         if (st == SLOT_TOMB && tomb_s == ~0ull) {
             tomb_s = s;
             tomb_meta = meta;
@@ -1254,10 +1273,7 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
             }
         }
         s = (s + 1) & mask;
-        if (++dist > mask) {
-            take_tomb();
-            break;
-        }
+        ++dist;
     }
     slot_of[i] = res;
     is_new[i] = fresh;
