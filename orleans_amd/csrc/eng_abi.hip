@@ -299,8 +299,8 @@ int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t 
     // the directory batches' own scratch (dir_scr): no bucketing left running on the bucket stream
     // shares it, so a batch need not wait for one (bfence) -- it overlaps the previous batch's bucketing
     GD_TRY(ensure_own(h, h->dir_scr[0], (size_t)n * 4));   // slot_of
-    GD_TRY(ensure_own(h, h->dir_scr[1], (size_t)n * 4));   // k_reg_find's seen metas, then win
-    GD_TRY(ensure_own(h, h->dir_scr[2], (size_t)n));       // is_new (k_reg_find writes every item's)
+    GD_TRY(ensure_own(h, h->dir_scr[1], (size_t)n * 4));   // k_reg_find_take's seen metas, then win
+    GD_TRY(ensure_own(h, h->dir_scr[2], (size_t)n));       // is_new (k_reg_find_take writes every item's)
     GD_TRY(slot_words(h));                                 // the per-slot election words
     const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
     uint32_t* slot_of = (uint32_t*)h->dir_scr[0].p;
@@ -316,7 +316,7 @@ int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t 
     const uint32_t* unsettled = nullptr;
     uint32_t* retry0 = nullptr;
     if (async) {
-        if (!h->reg_retry.p) {                     // gate counters: k_reg_take / the commit keep them
+        if (!h->reg_retry.p) {                     // gate counters: k_reg_find_take / the commit keep them
             GD_TRY(ensure_own(h, h->reg_retry, REG_PASSES * sizeof(uint32_t)));
             HIP_TRY(h, hipMemsetAsync(h->reg_retry.p, 0, REG_PASSES * sizeof(uint32_t), h->stream));
         }
@@ -340,13 +340,8 @@ int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t 
                       table_args(h), slot_of, is_new, win, &h->ctr->retry, (uint32_t*)nullptr, last));
         GD_TRY(pull_counters(h));
         // relaunches for the items that lost their CAS or met an unpublished claim
-        for (uint32_t pass = 1; h->ctr_host.retry && !h->ctr_host.err; ++pass) {
-            if (pass > 64) return set_err(h, GD_ETIMEOUT, "gd_dir_register: claims did not settle");
-            HIP_TRY(h, hipMemsetAsync(&h->ctr->retry, 0, sizeof(uint32_t), h->stream));
-            GD_TRY(launch(h, "k_reg_claim", g, b, 0, k_reg_claim, dk, n, h->slots, mask, h->ctr, slot_of, is_new, pass,
-                          dvals, table_args(h), last));
-            GD_TRY(pull_counters(h));
-        }
+        if (h->ctr_host.retry && !h->ctr_host.err)
+            GD_TRY(claim_passes(h, false, dk, n, slot_of, is_new, dvals, table_args(h), last, 1, "gd_dir_register"));
     }
     if (cx_inline(h, tt, n))                       // the winners project their slots as they commit
         GD_TRY(launch(h, "k_reg_commit", g, b, 0, k_reg_commit_elect_cx, (const uint32_t*)slot_of,
@@ -395,6 +390,26 @@ int slot_words(gd_handle* h) {
     GD_TRY(ensure_own(h, h->up_last, h->capacity * 4));
     HIP_TRY(h, hipMemsetAsync(h->up_last.p, 0, h->up_last.bytes, h->stream));
     return GD_OK;
+}
+
+// The read-back-driven claim passes of a batch (gd_dirbatch.h): k_reg_claim passes first_pass, first_pass + 1,
+// ... over the directory table (actdir: the activation directory's) until a pass defers no item or the
+// device reports an error; the counters' host copy (ctr_host / ad_host) is current on return.
+int claim_passes(gd_handle* h, bool actdir, const gd_key* dk, uint32_t n, uint32_t* slot_of, uint8_t* is_new,
+                 const gd_val* vals, const TableArgs& vt, uint32_t* last, uint32_t first_pass, const char* call) {
+    Slot* slots = actdir ? h->ad_slots : h->slots;
+    const unsigned long long mask = (actdir ? h->ad_cap : h->capacity) - 1;
+    DevCounters* ctr = actdir ? h->ad_ctr : h->ctr;
+    const DevCounters& host = actdir ? h->ad_host : h->ctr_host;
+    const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
+    for (uint32_t pass = first_pass;; ++pass) {
+        if (pass - first_pass >= 64) return set_err(h, GD_ETIMEOUT, "%s: claims did not settle", call);
+        HIP_TRY(h, hipMemsetAsync(&ctr->retry, 0, sizeof(uint32_t), h->stream));
+        GD_TRY(launch(h, "k_reg_claim", g, b, 0, k_reg_claim, dk, n, slots, mask, ctr, slot_of, is_new, pass, vals, vt,
+                      last));
+        GD_TRY(actdir ? ad_pull(h) : pull_counters(h));
+        if (host.retry == 0 || host.err) return GD_OK;
+    }
 }
 }  // namespace gdx
 
@@ -464,16 +479,10 @@ int gd_dir_upsert(gd_handle* h, const gd_key* keys, const gd_val* vals, uint32_t
     uint8_t* is_new = (uint8_t*)h->u8_a.p;
     uint32_t* last = (uint32_t*)h->up_last.p;
     const gd_key* dk = (const gd_key*)h->keys_in.p;
-    const unsigned long long mask = h->capacity - 1;
     TabTrack tt(h);                               // the batch re-projects its slots into the probe indexes
-    for (uint32_t pass = 0;; ++pass) {            // the registration's claim protocol (k_reg_claim)
-        HIP_TRY(h, hipMemsetAsync(&h->ctr->retry, 0, sizeof(uint32_t), h->stream));
-        GD_TRY(launch(h, "k_reg_claim", g, b, 0, k_reg_claim, dk, n, h->slots, mask, h->ctr, slot_of, is_new,
-                      pass, (const gd_val*)h->out_c.p, table_args(h), (uint32_t*)nullptr));
-        GD_TRY(pull_counters(h));
-        if (h->ctr_host.retry == 0 || h->ctr_host.err) break;
-        if (pass >= 64) return set_err(h, GD_ETIMEOUT, "gd_dir_upsert: claims did not settle");
-    }
+    // the registration's claim protocol; no election in the claims: the word is k_up_last's (1 + index)
+    GD_TRY(claim_passes(h, false, dk, n, slot_of, is_new, (const gd_val*)h->out_c.p, table_args(h), nullptr, 0,
+                        "gd_dir_upsert"));
     GD_TRY(launch(h, "k_up_last", g, b, 0, k_up_last, (const uint32_t*)slot_of, n, last));
     GD_TRY(launch(h, "k_up_apply", g, b, 0, k_up_apply, (const uint32_t*)slot_of, (const uint8_t*)is_new,
                   (const gd_val*)h->out_c.p, n, (const uint32_t*)last, h->slots, h->ctr, (uint8_t*)h->out_b.p,

@@ -347,20 +347,17 @@ int gd_actdir_add(gd_handle* h, const gd_key* act_ids, const uint32_t* ctx, cons
     uint32_t* slot_of = (uint32_t*)h->ad_buf[2].p;
     uint32_t* win = (uint32_t*)h->ad_buf[3].p;
     uint8_t* is_new = (uint8_t*)h->ad_buf[4].p;
-    for (uint32_t pass = 0;; ++pass) {            // TryAdd: the registration's claim protocol, first add wins
-        HIP_TRY(h, hipMemsetAsync(&h->ad_ctr->retry, 0, sizeof(uint32_t), h->stream));
-        GD_TRY(launch(h, "k_reg_claim", g, b, 0, k_reg_claim, dk, n, h->ad_slots, h->ad_cap - 1, h->ad_ctr, slot_of,
-                      is_new, pass, (const gd_val*)nullptr, TableArgs{}, (uint32_t*)nullptr));
-        GD_TRY(ad_pull(h));
-        if (h->ad_host.retry == 0 || h->ad_host.err) break;
-        if (pass >= 64) return set_err(h, GD_ETIMEOUT, "gd_actdir_add: claims did not settle");
-    }
-    GD_TRY(launch(h, "k_reg_minwin", g, b, 0, k_reg_minwin, (const uint32_t*)slot_of, (const uint8_t*)is_new, n,
-                  h->ad_slots));
-    GD_TRY(launch(h, "k_reg_resolve", g, b, 0, k_reg_resolve, (const uint32_t*)slot_of, (const uint8_t*)is_new, n,
-                  (const Slot*)h->ad_slots, win));
-    GD_TRY(launch(h, "k_reg_commit", g, b, 0, k_reg_commit, (const uint32_t*)slot_of, (const uint32_t*)win,
-                  (const gd_val*)h->ad_buf[1].p, n, h->ad_slots, h->ad_ctr, (uint32_t*)nullptr, 0u));
+    uint32_t* last = (uint32_t*)h->ad_last.p;
+    // TryAdd: the registration's claim protocol, the first add of a key wins (the election word, gd_dirbatch.h)
+    const int rc = claim_passes(h, true, dk, n, slot_of, is_new, nullptr, TableArgs{}, last, 0, "gd_actdir_add");
+    // unsettled: the claims made so far keep their words (pass 0 wrote every slot_of): zero them for the next call
+    if (rc == GD_ETIMEOUT) (void)launch(h, "k_up_clear", g, b, 0, k_up_clear, (const uint32_t*)slot_of, n, last);
+    if (rc != GD_OK) return rc;
+    // a device error (table full) goes through the commit, which clears every word the claims set: each
+    // has an elected item
+    GD_TRY(launch(h, "k_reg_commit", g, b, 0, k_reg_commit_elect, (const uint32_t*)slot_of, (const uint8_t*)is_new,
+                  (const gd_val*)h->ad_buf[1].p, n, h->ad_slots, h->ad_ctr, (uint32_t*)nullptr, 0u, last, win,
+                  (const uint32_t*)nullptr, (uint32_t*)nullptr));
     GD_TRY(launch(h, "k_reg_report", g, b, 0, k_reg_report, (const uint32_t*)slot_of, (const uint32_t*)win, n,
                   (const Slot*)h->ad_slots, (gd_val*)nullptr, (uint8_t*)h->ad_buf[5].p));
     if (out_added) HIP_TRY(h, hipMemcpyAsync(out_added, h->ad_buf[5].p, n, hipMemcpyDeviceToHost, h->stream));
@@ -382,12 +379,11 @@ int gd_actdir_remove(gd_handle* h, const gd_key* act_ids, uint32_t n, uint8_t* o
     GD_TRY(ensure(h, h->ad_buf[5], (size_t)n));
     const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
     uint32_t* slot_of = (uint32_t*)h->ad_buf[2].p;
-    // TryRemove: the first item of a key removes it (the unregistration election, gd_kernels.h)
-    GD_TRY(launch(h, "k_ad_find", g, b, 0, k_ad_find, (const gd_key*)h->ad_buf[0].p, n, ad_args(h), slot_of));
-    GD_TRY(launch(h, "k_unreg_poison", g, b, 0, k_unreg_poison, (const uint32_t*)slot_of, n, h->ad_slots));
-    GD_TRY(launch(h, "k_unreg_min", g, b, 0, k_unreg_min, (const uint32_t*)slot_of, n, h->ad_slots));
-    GD_TRY(launch(h, "k_unreg_commit", g, b, 0, k_unreg_commit, (const uint32_t*)slot_of, n, h->ad_slots, h->ad_ctr,
-                  (uint8_t*)h->ad_buf[5].p));
+    uint32_t* last = (uint32_t*)h->ad_last.p;
+    // TryRemove: the first item of a key removes it (the unregistration election, gd_dirbatch.h)
+    GD_TRY(launch(h, "k_ad_find", g, b, 0, k_ad_find, (const gd_key*)h->ad_buf[0].p, n, ad_args(h), slot_of, last));
+    GD_TRY(launch(h, "k_unreg_commit", g, b, 0, k_unreg_commit_elect, (const uint32_t*)slot_of, n, h->ad_slots,
+                  h->ad_ctr, last, (uint8_t*)h->ad_buf[5].p));
     if (out_removed) HIP_TRY(h, hipMemcpyAsync(out_removed, h->ad_buf[5].p, n, hipMemcpyDeviceToHost, h->stream));
     return sync(h);
 }
@@ -404,7 +400,8 @@ int gd_actdir_set_flags(gd_handle* h, const gd_key* act_ids, const uint8_t* flag
     const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
     uint32_t* slot_of = (uint32_t*)h->ad_buf[2].p;
     uint32_t* last = (uint32_t*)h->ad_last.p;
-    GD_TRY(launch(h, "k_ad_find", g, b, 0, k_ad_find, (const gd_key*)h->ad_buf[0].p, n, ad_args(h), slot_of));
+    GD_TRY(launch(h, "k_ad_find", g, b, 0, k_ad_find, (const gd_key*)h->ad_buf[0].p, n, ad_args(h), slot_of,
+                  (uint32_t*)nullptr));
     GD_TRY(launch(h, "k_up_last", g, b, 0, k_up_last, (const uint32_t*)slot_of, n, last));
     GD_TRY(launch(h, "k_ad_setflags", g, b, 0, k_ad_setflags, (const uint32_t*)slot_of, (const uint8_t*)h->ad_buf[1].p, n,
                   (const uint32_t*)last, h->ad_slots, (uint8_t*)h->ad_buf[5].p));

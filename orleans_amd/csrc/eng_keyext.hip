@@ -509,22 +509,13 @@ int merge_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, const int32_
     const uint32_t op = ++h->dir_op;
     GD_TRY(ensure(h, h->u32_a, (size_t)n * 4));   // slot_of
     GD_TRY(ensure(h, h->u8_a, (size_t)n));        // is_new
-    if (h->up_last.bytes < h->capacity * 4) {
-        GD_TRY(ensure(h, h->up_last, h->capacity * 4));
-        HIP_TRY(h, hipMemsetAsync(h->up_last.p, 0, h->up_last.bytes, h->stream));
-    }
+    GD_TRY(slot_words(h));
     HIP_TRY(h, hipMemsetAsync(h->u8_a.p, 0, n, h->stream));
     const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
     uint32_t* slot_of = (uint32_t*)h->u32_a.p;
     uint8_t* is_new = (uint8_t*)h->u8_a.p;
-    for (uint32_t pass = 0;; ++pass) {            // the registration's claim protocol; no IsValidSilo check in Merge
-        HIP_TRY(h, hipMemsetAsync(&h->ctr->retry, 0, sizeof(uint32_t), h->stream));
-        GD_TRY(launch(h, "k_reg_claim", g, b, 0, k_reg_claim, dk, n, h->slots, h->capacity - 1, h->ctr, slot_of,
-                      is_new, pass, (const gd_val*)nullptr, table_args(h), (uint32_t*)nullptr));
-        GD_TRY(pull_counters(h));
-        if (h->ctr_host.retry == 0 || h->ctr_host.err) break;
-        if (pass >= 64) return set_err(h, GD_ETIMEOUT, "gd_dir_merge: claims did not settle");
-    }
+    // the registration's claim protocol (no IsValidSilo check in Merge); the word is k_dup_mark's
+    GD_TRY(claim_passes(h, false, dk, n, slot_of, is_new, nullptr, table_args(h), nullptr, 0, "gd_dir_merge"));
     uint32_t* last = (uint32_t*)h->up_last.p;
     GD_TRY(launch(h, "k_dup_mark", g, b, 0, k_dup_mark, (const uint32_t*)slot_of, n, last, h->ctr));
     GD_TRY(launch(h, "k_up_clear", g, b, 0, k_up_clear, (const uint32_t*)slot_of, n, last));

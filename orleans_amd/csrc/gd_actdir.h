@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "gd_common.h"
+#include "gd_dirbatch.h"
 #include "gd_frames.h"
 #include "gd_kernels.h"
 
@@ -45,9 +46,10 @@ __device__ __forceinline__ bool ad_find(const AdArgs& t, uint64_t n0, uint64_t n
     return f;
 }
 
-// Slot of each key (TryRemove / state updates): NONE32 if absent.
+// Slot of each key (TryRemove / state updates): NONE32 if absent.  last (optional, TryRemove): the find also
+// elects the first item of each slot (atomicMax(~i), as unreg_find_elect_item) for k_unreg_commit_elect.
 static __global__ void __launch_bounds__(BLOCK) k_ad_find(const gd_key* __restrict__ keys, uint32_t n, AdArgs t,
-                                                   uint32_t* __restrict__ slot_of) {
+                                                   uint32_t* __restrict__ slot_of, uint32_t* __restrict__ last) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
@@ -64,6 +66,7 @@ static __global__ void __launch_bounds__(BLOCK) k_ad_find(const gd_key* __restri
         s = (s + 1) & t.mask;
     }
     slot_of[i] = res;
+    if (last && res != NONE32) atomicMax(&last[res], ~i);
 }
 
 static __global__ void __launch_bounds__(BLOCK) k_ad_lookup(const gd_key* __restrict__ keys, uint32_t n, AdArgs t,

@@ -18,6 +18,7 @@
 
 #include "gd_cache.h"
 #include "gd_common.h"
+#include "gd_dirbatch.h"
 #include "gd_kernels.h"
 
 namespace gd {

@@ -371,6 +371,8 @@ int unregister_core(gd_handle* h, const gd_key* dk, const uint32_t* dacts, uint3
 int maybe_grow_async(gd_handle* h, uint64_t incoming);
 int bfence(gd_handle* h);
 int slot_words(gd_handle* h);
+int claim_passes(gd_handle* h, bool actdir, const gd_key* dk, uint32_t n, uint32_t* slot_of, uint8_t* is_new,
+                 const gd_val* vals, const TableArgs& vt, uint32_t* last, uint32_t first_pass, const char* call);
 int split_count(gd_handle* h, const uint8_t* keep, uint32_t n_keep, uint64_t* total);
 uint64_t grain_tcd(int32_t type_code);
 int fan_count(gd_handle* h, const uint32_t* row_off, uint32_t n_nodes, const uint32_t* frontier, uint32_t nf,

@@ -8,6 +8,7 @@
 //                            open-addressing directory (GrainDirectoryPartition.cs:385-441).
 //   K3        k_radix_*      stable LSD partition of message indices by activation
 //                            (ActivationData.cs:566-606 per-activation FIFO), reduce-then-scan.
+// The batches that change the directory table (register, upsert, unregister, rehash): gd_dirbatch.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -869,710 +870,6 @@ static __global__ void __launch_bounds__(BLOCK) k_ring_hashes(const uint32_t* __
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     out_silo[i] = s_own[ring_position<MODE>(s_pts, ring.n, ring.top, hashes[i])];
-}
-
-// ------------------------------------------------------------------ directory maintenance
-// AddSingleActivation (GrainDirectoryPartition.cs:304-326, GrainInfo :110-124) for a batch.
-// Phase 1: find the key's slot or claim a free one.  A lane that meets a slot
-// another lane has claimed in this launch reads the claimer off the slot's
-// election word and joins it (its twin) or walks on (another key); a lane that
-// loses the CAS on its free slot walks on from that slot in the same pass.  Only
-// a lane that finds the election word still zero does NOT wait (a divergent
-// wait can starve the claimer of the same wave once the compiler sinks its
-// publish to the loop exit): it is marked RETRY and the host relaunches the
-// kernel for the retried items, after the kernel boundary has published every
-// claim.  "Claimed in this launch" is read off the meta alone (round 6): CLAIMED, or
-// PENDING with this launch's tag in the silo field (claim_tag) -- a PENDING slot of
-// an earlier launch has its key published by that launch's end.  So a claim needs no
-// release fence (an agent-scope release writes the XCD's L2 back, per wave) and a
-// walk no acquire loads (an agent-scope acquire invalidates it): the metas are read
-// and swapped with relaxed device-coherent atomics, the keys with plain loads.
-constexpr uint32_t SLOT_RETRY = 0xFFFFFFFEu;
-// PENDING's tag of claim launch `pass` (k_reg_take's claims carry 0)
-__device__ __forceinline__ uint32_t claim_tag(uint32_t pass) { return (pass + 1u) & 0xFFFFu; }
-
-// vals / valid (nullable): an item whose silo is not valid is skipped (slot_of = NONE32): the
-// IsValidSilo check of AddSingleActivation / AddActivation (GrainDirectoryPartition.cs:279,310).
-__device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restrict__ keys, Slot* slots,
-                                               unsigned long long mask, DevCounters* ctr,
-                                               uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
-                                               const gd_val* __restrict__ vals, const TableArgs& vt, uint32_t* retry,
-                                               uint32_t& pdist, bool& reused, uint32_t tag,
-                                               uint32_t* __restrict__ last = nullptr);
-// The claims' counter updates, one atomic a wave (one per item queued ~10^4 same-address atomics behind a
-// 1 % registration batch: 0.12 ms of it at cfg 2).  Every lane of the wave calls it.
-__device__ __forceinline__ void claim_counters(DevCounters* ctr, uint32_t pdist, bool reused) {
-    for (int off = WAVE / 2; off > 0; off >>= 1) pdist = max(pdist, (uint32_t)__shfl_xor(pdist, off, WAVE));
-    const unsigned long long m = __ballot(reused);
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        // max_probe only grows: a wave whose distance is not past it (nearly all) skips the atomic
-        if (pdist && pdist > __hip_atomic_load(&ctr->max_probe, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
-            atomicMax(&ctr->max_probe, pdist);
-        if (m) atomicAdd(ctr_stripe(ctr) + 1, ~(unsigned long long)__popcll(m) + 1ull);   // tomb - reused
-    }
-}
-
-// last (optional): one word per table slot, zero between batches -- an item that ends with a new entry
-// (claimed it, or found it PENDING) elects itself: atomicMax(~i), so the lowest batch index wins
-// (k_reg_commit_elect); null: the k_reg_minwin / k_reg_resolve election on the slot's act word.
-static __global__ void __launch_bounds__(BLOCK) k_reg_claim(const gd_key* __restrict__ keys, uint32_t n, Slot* slots,
-                                                     unsigned long long mask, DevCounters* ctr,
-                                                     uint32_t* __restrict__ slot_of,
-                                                     uint8_t* __restrict__ is_new, uint32_t pass,
-                                                     const gd_val* __restrict__ vals, TableArgs vt,
-                                                     uint32_t* __restrict__ last = nullptr) {
-    // pass 0: every item; later passes: the items the previous one deferred
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    uint32_t pd = 0;
-    bool reused = false;
-    if (i < n && (pass == 0 || slot_of[i] == SLOT_RETRY)) {
-        reg_claim_item(i, keys, slots, mask, ctr, slot_of, is_new, vals, vt, &ctr->retry, pd, reused,
-                       claim_tag(pass), last);
-        if (last && is_new[i]) atomicMax(&last[slot_of[i]], ~i);
-    }
-    claim_counters(ctr, pd, reused);
-}
-
-// k_reg_take + the gated claim passes of an asynchronous batch.  k_reg_take settles one new grain of each
-// group colliding on a first free slot and defers the others; a claim pass settles every item it runs
-// except those that read a fresh claim's election word before it was written (they defer again), so the
-// passes after the first are a margin for that window, wider in a large batch (300,000 new grains in a
-// 2M-slot table have needed more than 3)
-constexpr uint32_t REG_PASSES = 12;
-constexpr uint32_t REG_PASSES_SMALL = 4;    // ... for a batch of at most 2^16 items
-// The claim pass of an asynchronous batch (gd_dir_register_device_async): pass p > 0 runs only when
-// pass p - 1 deferred items (gate = its retry count; all lanes read the same word), so the host enqueues
-// REG_PASSES passes without reading a count back; k_reg_settled flags a batch still unsettled after them.
-static __global__ void __launch_bounds__(BLOCK) k_reg_claim_gated(const gd_key* __restrict__ keys, uint32_t n,
-                                                           Slot* slots, unsigned long long mask, DevCounters* ctr,
-                                                           uint32_t* __restrict__ slot_of,
-                                                           uint8_t* __restrict__ is_new,
-                                                           const gd_val* __restrict__ vals, TableArgs vt,
-                                                           const uint32_t* __restrict__ gate, uint32_t* retry,
-                                                           uint32_t* __restrict__ last, uint32_t pass) {
-    if (gate && *gate == 0) return;
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    // pass 0 zeroes the later passes' counters (its own, retry[0], was zeroed by the previous batch's
-    // k_reg_minwin_gated, or at allocation)
-    if (!gate && i < REG_PASSES - 1) retry[1 + i] = 0;
-    uint32_t pd = 0;
-    bool reused = false;
-    if (i < n && (!gate || slot_of[i] == SLOT_RETRY)) {
-        reg_claim_item(i, keys, slots, mask, ctr, slot_of, is_new, vals, vt, retry, pd, reused, claim_tag(pass),
-                       last);
-        if (is_new[i]) atomicMax(&last[slot_of[i]], ~i);    // the election (k_reg_commit_elect)
-    }
-    claim_counters(ctr, pd, reused);
-}
-// The claim as two kernels (round 6; the single claim kernel walked each chain with agent-scope atomic
-// loads, two dependent L2 round trips a slot, 0.08 ms for a 10^4-item batch at cfg 2):
-//   k_reg_find  read-only (nothing writes the table during it): each item's existing entry, or the first
-//               free slot of its chain (its first tombstone, else the empty slot ending it) and that
-//               slot's meta, with plain loads;
-//   k_reg_take  one CAS on that slot from the meta seen; an item that loses it (another item of the
-//               batch took the slot: the same key or a colliding one) is deferred to the gated claim
-//               passes (k_reg_claim_gated, the full protocol).
-constexpr uint8_t REG_CANDIDATE = 2;        // is_new: k_reg_find left a free slot to take
-// LIVE_CLAIMS (k_reg_find_take): other items of the launch claim slots while this one walks -- a slot
-// CLAIMED or PENDING holds a key unpublished to this launch, whose claimer the slot's election word
-// names (last): this key's twin -- join it (is_new 1) -- or another key -- walk on; a claim not yet
-// recorded defers the item (SLOT_RETRY).  A stale EMPTY or tombstone in a cached line only makes the
-// take's CAS fail (the CAS is the arbiter).
-template <bool LIVE_CLAIMS = false>
-__device__ __forceinline__ void reg_find_item(uint32_t i, const gd_key* __restrict__ keys,
-                                              const Slot* __restrict__ slots, unsigned long long mask,
-                                              DevCounters* ctr, uint32_t* __restrict__ slot_of,
-                                              uint8_t* __restrict__ is_new, uint32_t* __restrict__ seen,
-                                              const gd_val* __restrict__ vals, const TableArgs& vt,
-                                              uint32_t* __restrict__ last = nullptr) {
-    if (vals && !tab_silo_valid(vt, vals[i].silo)) {
-        slot_of[i] = NONE32;
-        is_new[i] = 0;
-        return;
-    }
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
-    unsigned long long free_s = ~0ull;
-    uint32_t free_meta = 0, res = NONE32;
-    uint8_t st_out = 0;
-    // four slots (one 128-B line) a step: homes are 8-slot aligned, so a chain is mostly one or two steps
-    bool done = false;
-    for (unsigned long long dist = 0; !done && dist <= mask; dist += 4) {
-        uint4 q[8];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint4* p = reinterpret_cast<const uint4*>(slots + ((s + k) & mask));
-            q[2 * k] = p[0];
-            q[2 * k + 1] = p[1];
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (done) continue;
-            const uint4 a = q[2 * k], b = q[2 * k + 1];
-            const uint32_t st = slot_state(b.w);
-            const unsigned long long sk = (s + k) & mask;
-            if (st == SLOT_EMPTY) {
-                if (free_s == ~0ull) {
-                    free_s = sk;
-                    free_meta = b.w;
-                }
-                done = true;
-            } else if (LIVE_CLAIMS && (st == SLOT_CLAIMED || st == SLOT_PENDING)) {
-                const uint32_t w = __hip_atomic_load(&last[sk], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (w == 0) {
-                    res = SLOT_RETRY;                    // a claim of this launch not yet recorded
-                    done = true;
-                } else {
-                    const gd_key& c = keys[~w];
-                    if (c.n0 == n0 && c.n1 == n1 && c.type_code_data == tcd) {
-                        res = (uint32_t)sk;              // the twin's claim: join it
-                        st_out = 1;
-                        done = true;
-                    }                                    // else another key's claim: walk on
-                }
-            } else {
-                if (st == SLOT_TOMB && free_s == ~0ull) {
-                    free_s = sk;
-                    free_meta = b.w;
-                }
-                if (st == SLOT_LIVE && ((uint64_t)a.x | ((uint64_t)a.y << 32)) == n0 &&
-                    ((uint64_t)a.z | ((uint64_t)a.w << 32)) == n1 && ((uint64_t)b.x | ((uint64_t)b.y << 32)) == tcd) {
-                    res = (uint32_t)sk;                  // registered already
-                    done = true;
-                }
-            }
-        }
-        s = (s + 4) & mask;
-    }
-    if (res == NONE32 && !(LIVE_CLAIMS && st_out == 1)) {
-        if (free_s == ~0ull) {
-            atomicOr(&ctr->err, 2u);                     // no free slot: the table is full
-        } else {
-            res = (uint32_t)free_s;
-            seen[i] = free_meta;
-            st_out = REG_CANDIDATE;
-        }
-    }
-    slot_of[i] = res;
-    is_new[i] = st_out;
-}
-static __global__ void __launch_bounds__(BLOCK) k_reg_find(const gd_key* __restrict__ keys, uint32_t n,
-                                                    const Slot* __restrict__ slots, unsigned long long mask,
-                                                    DevCounters* ctr, uint32_t* __restrict__ slot_of,
-                                                    uint8_t* __restrict__ is_new, uint32_t* __restrict__ seen,
-                                                    const gd_val* __restrict__ vals, TableArgs vt) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) reg_find_item(i, keys, slots, mask, ctr, slot_of, is_new, seen, vals, vt);
-}
-
-// k_reg_take's item: one CAS on the slot k_reg_find left (pd / reused for claim_counters; deferred: the
-// item lost the CAS and goes to the next claim pass).
-__device__ __forceinline__ void reg_take_item(uint32_t i, const gd_key* __restrict__ keys, Slot* slots,
-                                              unsigned long long mask, uint32_t* __restrict__ slot_of,
-                                              uint8_t* __restrict__ is_new, const uint32_t* __restrict__ seen,
-                                              uint32_t* __restrict__ last, uint32_t& pd, bool& reused,
-                                              bool& deferred) {
-    if (is_new[i] == REG_CANDIDATE) {
-        const uint32_t t = slot_of[i];
-        uint32_t expected = seen[i];
-        uint32_t* mp = &slots[t].meta;
-        if (__hip_atomic_compare_exchange_strong(mp, &expected, make_meta(SLOT_CLAIMED, 0), __ATOMIC_RELAXED,
-                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            // No item of this launch reads a slot another item claimed (k_reg_find read the table before it,
-            // a CAS loser defers below), so the key needs no release here: the kernel's end publishes it to
-            // the passes and commit that read it (an agent-scope release fence writes the XCD's L2 back,
-            // per wave: 2.2 ns an item at cfg 3's 100M registrations, 72 ms a 33M batch)
-            atomicMax(&last[t], ~i);                     // the election (k_reg_commit_elect), and the claimer
-            const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-            Slot& sl = slots[t];
-            sl.n0 = n0;
-            sl.n1 = n1;
-            sl.tcd = tcd;
-            sl.act = NONE32;
-            __hip_atomic_store(mp, make_meta(SLOT_PENDING, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long home = home_slot(uniform_hash(n0, n1, tcd), mask);
-            pd = (uint32_t)((t - home) & mask);
-            reused = slot_state(seen[i]) == SLOT_TOMB;
-            is_new[i] = 1;
-        } else {
-            // taken meanwhile (another new grain homed nearby, or this key's twin, whose key this launch
-            // has not published): the full protocol in the next claim pass
-            slot_of[i] = SLOT_RETRY;
-            is_new[i] = 0;
-            deferred = true;
-        }
-    }
-}
-// The deferred items' count, one atomic a wave (every lane of the wave calls it).
-__device__ __forceinline__ void count_deferred(uint32_t* retry, bool deferred) {
-    const unsigned long long dm = __ballot(deferred);
-    if ((threadIdx.x & (WAVE - 1)) == 0 && dm) atomicAdd(retry, (uint32_t)__popcll(dm));
-}
-static __global__ void __launch_bounds__(BLOCK) k_reg_take(const gd_key* __restrict__ keys, uint32_t n, Slot* slots,
-                                                    unsigned long long mask, DevCounters* ctr,
-                                                    const gd_val* __restrict__ vals, TableArgs vt,
-                                                    uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
-                                                    const uint32_t* __restrict__ seen, uint32_t* retry,
-                                                    uint32_t* zero, uint32_t* __restrict__ last) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (zero && i < REG_PASSES - 1) zero[i] = 0;         // the gated passes' counters (asynchronous batches)
-    uint32_t pd = 0;
-    bool reused = false, deferred = false;
-    if (i < n) reg_take_item(i, keys, slots, mask, slot_of, is_new, seen, last, pd, reused, deferred);
-    count_deferred(retry, deferred);
-    claim_counters(ctr, pd, reused);
-}
-// k_reg_find and k_reg_take as one launch (round 6): each item walks with plain loads and takes its free
-// slot at once; an item whose walk meets a claim of this launch defers to the claim passes.
-static __global__ void __launch_bounds__(BLOCK) k_reg_find_take(const gd_key* __restrict__ keys, uint32_t n,
-                                                         Slot* slots, unsigned long long mask, DevCounters* ctr,
-                                                         const gd_val* __restrict__ vals, TableArgs vt,
-                                                         uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
-                                                         uint32_t* __restrict__ seen, uint32_t* retry, uint32_t* zero,
-                                                         uint32_t* __restrict__ last) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (zero && i < REG_PASSES - 1) zero[i] = 0;         // the gated passes' counters (asynchronous batches)
-    uint32_t pd = 0;
-    bool reused = false, deferred = false;
-    if (i < n) {
-        reg_find_item<true>(i, keys, slots, mask, ctr, slot_of, is_new, seen, vals, vt, last);
-        if (slot_of[i] == SLOT_RETRY) deferred = true;
-        else if (is_new[i] == 1) atomicMax(&last[slot_of[i]], ~i);      // joined its twin's claim
-        else reg_take_item(i, keys, slots, mask, slot_of, is_new, seen, last, pd, reused, deferred);
-    }
-    count_deferred(retry, deferred);
-    claim_counters(ctr, pd, reused);
-}
-
-constexpr uint32_t ERR_UNSETTLED = 64u;     // DevCounters::err: an asynchronous batch's claims did not settle
-// k_reg_minwin for an asynchronous batch: also flags claims still deferred after the last gated pass
-// (ERR_UNSETTLED) and zeroes pass 0's counter for the next batch.
-static __global__ void __launch_bounds__(BLOCK) k_reg_minwin_gated(const uint32_t* __restrict__ slot_of,
-                                                            const uint8_t* __restrict__ is_new, uint32_t n, Slot* slots,
-                                                            uint32_t* retry, DevCounters* ctr) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i == 0) {
-        if (retry[REG_PASSES - 1]) atomicOr(&ctr->err, ERR_UNSETTLED);
-        retry[0] = 0;
-    }
-    if (i >= n || !is_new[i]) return;
-    atomicMin(&slots[slot_of[i]].act, i);
-}
-
-__device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restrict__ keys, Slot* slots,
-                                               unsigned long long mask, DevCounters* ctr,
-                                               uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
-                                               const gd_val* __restrict__ vals, const TableArgs& vt, uint32_t* retry,
-                                               uint32_t& pdist, bool& reused, uint32_t tag,
-                                               uint32_t* __restrict__ last) {
-    if (vals && !tab_silo_valid(vt, vals[i].silo)) {
-        slot_of[i] = NONE32;
-        is_new[i] = 0;
-        return;
-    }
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
-    unsigned long long dist = 0;
-    uint32_t res = NONE32;
-    uint8_t fresh = 0;
-    // The key's first tombstone, reused when the chain does not hold the key (round 6: a directory under
-    // continuous RemoveActivation / AddSingleActivation churn no longer fills with tombstones until a
-    // rehash).  Every item of one key meets the same first free slot, and a claim is a CAS, so a key is
-    // never placed twice.  An item that loses its free slot (the tombstone, or the empty slot ending the
-    // chain) to another item of the launch walks on from that slot in the same pass: it meets the winner's
-    // claim there -- its twin's: join it; another key's: the chain's next free slot is the next try.  (Deferred
-    // to the next pass instead, k new grains of a batch sharing a chain took k passes, and an asynchronous
-    // batch has REG_PASSES_SMALL.)
-    unsigned long long tomb_s = ~0ull, tomb_dist = 0;
-    uint32_t tomb_meta = 0;
-    for (;;) {
-        uint32_t* meta_p = &slots[s].meta;
-        const uint32_t meta = __hip_atomic_load(meta_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st = slot_state(meta);
-        // the chain ends (an empty slot, or the whole table walked) without a copy of the key
-        const bool ends = st == SLOT_EMPTY || dist > mask;
-        if (ends && st != SLOT_EMPTY && tomb_s == ~0ull) {
-            atomicOr(&ctr->err, 2u);                         // no free slot: the table is full
-            break;
-        }
-        bool won = false;
-        const bool tomb = tomb_s != ~0ull;
-        const unsigned long long t = tomb ? tomb_s : s, d = tomb ? tomb_dist : dist;
-        if (ends) {
-            // claim slot t for the key: the claimer's index in the slot's election word (readable by this
-            // launch's walks), the key, then PENDING with this launch's tag (read as unpublished by this
-            // launch's other items; published to later launches by the kernel boundary)
-            uint32_t expected = tomb ? tomb_meta : meta;
-            uint32_t* mp = &slots[t].meta;
-            won = __hip_atomic_compare_exchange_strong(mp, &expected, make_meta(SLOT_CLAIMED, 0), __ATOMIC_RELAXED,
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (won) {
-                if (last) atomicMax(&last[t], ~i);
-                Slot& sl = slots[t];
-                sl.n0 = n0;
-                sl.n1 = n1;
-                sl.tcd = tcd;
-                sl.act = NONE32;
-                __hip_atomic_store(mp, make_meta(SLOT_PENDING, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        // The winner's writes above stay inside the loop: the wave's losers of the same slot read the election
-        // word in their next iteration.  Without this join the winner's block only leads out of the loop, and
-        // a divergent wave runs such a block after its last lane has left the loop -- after the losers had
-        // read a zero word and deferred, one settled item a wave and pass.  The builtin emits no instruction:
-        // it is a convergent call the compiler does not duplicate, which keeps the join one block of the
-        // loop.  That is a property of code generation, not of the memory model, and correctness does not
-        // rest on it (a loser that reads a zero word defers, as before): a compiler that moves the block out
-        // again brings back the k-passes behaviour silently, and tests/test_gpu_dir_chains.py's asynchronous
-        // cases (20 new grains on one tombstoned chain in 4 passes) then fail with GD_ETIMEOUT.
-        __builtin_amdgcn_wave_barrier();
-        if (won) {
-            pdist = (uint32_t)d;                             // max_probe: claim_counters
-            reused = tomb;                                   // tomb - 1: claim_counters
-            res = (uint32_t)t;
-            fresh = 1;
-            break;
-        }
-        if (ends) {
-            // lost slot t: walk on from it (an empty slot that was lost is read again as it is)
-            s = t;
-            dist = d;
-            tomb_s = ~0ull;
-            continue;
-        }
-        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && slot_silo(meta) == tag);
-        if (unpublished) {
-            // claimed in this launch: its key is not published to this launch, but its claimer is (the slot's
-            // election word, written right after the claim): the key's twin -- join it -- or another key's
-            // claim -- walk on.  Only a claim whose word is not yet visible defers the item (no wait: the
-            // claimer may be a lane of this wave).
-            const uint32_t w = last ? __hip_atomic_load(&last[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-            if (w == 0) {
-                res = SLOT_RETRY;
-                atomicAdd(retry, 1u);
-                break;
-            }
-            const gd_key& c = keys[~w];
-            if (c.n0 == n0 && c.n1 == n1 && c.type_code_data == tcd) {
-                res = (uint32_t)s;
-                fresh = 1;
-                break;
-            }
-        }
-        if (st == SLOT_TOMB && tomb_s == ~0ull) {
-            tomb_s = s;
-            tomb_meta = meta;
-            tomb_dist = dist;
-        }
-        if (!unpublished && (st == SLOT_LIVE || st == SLOT_PENDING)) {   // a key published before this launch
-            const uint64_t k0 = slots[s].n0, k1 = slots[s].n1, k2 = slots[s].tcd;
-            if (k0 == n0 && k1 == n1 && k2 == tcd) {
-                res = (uint32_t)s;
-                fresh = (st == SLOT_PENDING) ? 1 : 0;
-                break;
-            }
-        }
-        s = (s + 1) & mask;
-        ++dist;
-    }
-    slot_of[i] = res;
-    is_new[i] = fresh;
-}
-
-// Phase 2: the lowest batch index among the items of a new entry wins (sequential
-// "first registration wins" order).
-static __global__ void __launch_bounds__(BLOCK) k_reg_minwin(const uint32_t* __restrict__ slot_of,
-                                                      const uint8_t* __restrict__ is_new, uint32_t n, Slot* slots) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n || !is_new[i]) return;
-    atomicMin(&slots[slot_of[i]].act, i);   // is_new implies a real slot index
-}
-
-static __global__ void __launch_bounds__(BLOCK) k_reg_resolve(const uint32_t* __restrict__ slot_of,
-                                                       const uint8_t* __restrict__ is_new, uint32_t n,
-                                                       const Slot* slots, uint32_t* __restrict__ win) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    win[i] = is_new[i] ? slots[slot_of[i]].act : NONE32;
-}
-
-__device__ __forceinline__ void reg_commit_item(uint32_t i, const uint32_t* __restrict__ slot_of,
-                                                const gd_val* __restrict__ vals, Slot* slots, DevCounters* ctr,
-                                                uint32_t* __restrict__ vtag, uint32_t op);
-// live (+1 an insert, or -1 and tomb +1 a removal) for the wave's flagged lanes, one atomic each a wave.
-// Every lane of the wave calls it.
-__device__ __forceinline__ void live_delta(DevCounters* ctr, bool flag, bool removal) {
-    const unsigned long long m = __ballot(flag);
-    if ((threadIdx.x & (WAVE - 1)) != 0 || !m) return;
-    const unsigned long long c = (unsigned long long)__popcll(m);
-    unsigned long long* st = ctr_stripe(ctr);        // folded into live / tomb by k_ctr_fold
-    atomicAdd(st, removal ? ~c + 1ull : c);
-    if (removal) atomicAdd(st + 1, c);
-}
-static __global__ void __launch_bounds__(BLOCK) k_reg_commit(const uint32_t* __restrict__ slot_of,
-                                                      const uint32_t* __restrict__ win,
-                                                      const gd_val* __restrict__ vals, uint32_t n, Slot* slots,
-                                                      DevCounters* ctr, uint32_t* __restrict__ vtag, uint32_t op) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool w = i < n && win[i] == i;
-    if (w) reg_commit_item(i, slot_of, vals, slots, ctr, vtag, op);
-    live_delta(ctr, w, false);
-}
-// The commit of a batch elected by `last` (k_reg_take / the claim passes): item i commits when it holds its
-// slot's word (~i), clears the word for the next batch, and records win[i] (i or NONE32) for k_reg_report.
-// unsettled (optional): the last gated pass's deferred count -- a batch still unsettled flags ERR_UNSETTLED
-// -- and retry0, zeroed here for the next batch (k_reg_take counts into it).
-__device__ __forceinline__ bool reg_elected(uint32_t i, uint32_t n, const uint32_t* __restrict__ slot_of,
-                                            const uint8_t* __restrict__ is_new, uint32_t* __restrict__ last,
-                                            uint32_t* __restrict__ win) {
-    if (i >= n) return false;
-    bool w = false;
-    if (is_new[i]) {
-        const uint32_t s = slot_of[i];
-        w = last[s] == ~i;
-        if (w) last[s] = 0;                              // losers read ~winner or 0: never their own
-    }
-    win[i] = w ? i : NONE32;
-    return w;
-}
-__device__ __forceinline__ void reg_commit_item(uint32_t i, const uint32_t* __restrict__ slot_of,
-                                                const gd_val* __restrict__ vals, Slot* slots, DevCounters* ctr,
-                                                uint32_t* __restrict__ vtag, uint32_t op) {
-    Slot& sl = slots[slot_of[i]];
-    if (vals[i].silo > 0xFFFEu) atomicOr(&ctr->err, 4u);   // silo index out of range (device-side values)
-    sl.act = vals[i].act;
-    sl.meta = make_meta(SLOT_LIVE, vals[i].silo);
-    // GrainInfo.AddSingleActivation: SingleInstance = true, VersionTag = rand.Next() (:110-124)
-    if (vtag) vtag[slot_of[i]] = VTAG_SINGLE | version_tag(op, uniform_hash(sl.n0, sl.n1, sl.tcd));
-}
-
-static __global__ void __launch_bounds__(BLOCK) k_reg_commit_elect(const uint32_t* __restrict__ slot_of,
-                                                            const uint8_t* __restrict__ is_new,
-                                                            const gd_val* __restrict__ vals, uint32_t n, Slot* slots,
-                                                            DevCounters* ctr, uint32_t* __restrict__ vtag, uint32_t op,
-                                                            uint32_t* __restrict__ last, uint32_t* __restrict__ win,
-                                                            const uint32_t* __restrict__ unsettled,
-                                                            uint32_t* __restrict__ retry0) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i == 0 && unsettled) {
-        if (*unsettled) atomicOr(&ctr->err, ERR_UNSETTLED);
-        *retry0 = 0;                                     // k_reg_take's counter, for the next batch
-    }
-    const bool w = reg_elected(i, n, slot_of, is_new, last, win);
-    if (w) reg_commit_item(i, slot_of, vals, slots, ctr, vtag, op);
-    live_delta(ctr, w, false);
-}
-
-
-// gd_dir_upsert: the last batch item of each slot wins (batch order), then writes its value.
-// `last` (one u32 per table slot, zero between calls) holds 1 + the winning index.
-static __global__ void __launch_bounds__(BLOCK) k_up_last(const uint32_t* __restrict__ slot_of, uint32_t n,
-                                                   uint32_t* __restrict__ last) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n || slot_of[i] >= SLOT_RETRY) return;
-    atomicMax(&last[slot_of[i]], i + 1);
-}
-static __global__ void __launch_bounds__(BLOCK) k_up_apply(const uint32_t* __restrict__ slot_of,
-                                                    const uint8_t* __restrict__ is_new, const gd_val* __restrict__ vals,
-                                                    uint32_t n, const uint32_t* __restrict__ last, Slot* slots,
-                                                    DevCounters* ctr, uint8_t* __restrict__ out_inserted,
-                                                    uint32_t* __restrict__ vtag, uint32_t op) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = slot_of[i];
-    uint8_t ins = 0;
-    if (s < SLOT_RETRY && last[s] == i + 1) {
-        Slot& sl = slots[s];
-        // GrainInfo.AddActivation (:89-108): a new tag unless the same activation is refreshed on the
-        // same silo; the entry is no longer in single-instance mode
-        const bool same = !is_new[i] && sl.act == vals[i].act && slot_silo(sl.meta) == vals[i].silo;
-        if (vtag && !same) vtag[s] = version_tag(op, uniform_hash(sl.n0, sl.n1, sl.tcd));
-        sl.act = vals[i].act;
-        sl.meta = make_meta(SLOT_LIVE, vals[i].silo);
-        if (is_new[i]) {
-            atomicAdd(&ctr->live, 1ull);
-            ins = 1;
-        }
-    }
-    out_inserted[i] = ins;
-}
-static __global__ void __launch_bounds__(BLOCK) k_up_clear(const uint32_t* __restrict__ slot_of, uint32_t n,
-                                                    uint32_t* __restrict__ last) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n && slot_of[i] < SLOT_RETRY) last[slot_of[i]] = 0;
-}
-
-static __global__ void __launch_bounds__(BLOCK) k_reg_report(const uint32_t* __restrict__ slot_of,
-                                                      const uint32_t* __restrict__ win, uint32_t n,
-                                                      const Slot* slots, gd_val* __restrict__ out_vals,
-                                                      uint8_t* __restrict__ out_inserted) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t s = slot_of[i];
-    if (s >= SLOT_RETRY) {
-        if (out_vals) out_vals[i] = gd_val{NONE32, NONE32};
-        if (out_inserted) out_inserted[i] = 0;
-        return;
-    }
-    const Slot sl = slots[s];
-    if (out_vals) out_vals[i] = gd_val{sl.act, slot_silo(sl.meta)};
-    if (out_inserted) out_inserted[i] = (win[i] == i) ? 1 : 0;
-}
-
-// RemoveActivation (GrainDirectoryPartition.cs:335-363, Force): find the live entry
-// whose single activation matches; the first matching item of the batch removes it.
-static __global__ void __launch_bounds__(BLOCK) k_unreg_find(const gd_key* __restrict__ keys,
-                                                      const uint32_t* __restrict__ acts, uint32_t n,
-                                                      const Slot* slots, unsigned long long mask,
-                                                      const DevCounters* ctr, uint32_t* __restrict__ slot_of) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    const uint32_t h = uniform_hash(n0, n1, tcd);
-    unsigned long long s = home_slot(h, mask);
-    uint32_t res = NONE32;
-    for (uint32_t p = 0; p <= ctr->max_probe; ++p) {
-        const Slot sl = slots[s];
-        const uint32_t st = slot_state(sl.meta);
-        if (st == SLOT_EMPTY) break;
-        if (st == SLOT_LIVE && sl.n0 == n0 && sl.n1 == n1 && sl.tcd == tcd) {
-            if (sl.act == acts[i]) res = (uint32_t)s;
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    slot_of[i] = res;
-}
-
-// RemoveActivation with the election in a per-slot word (round 6: 2 launches instead of 4): the find also
-// elects the first matching item of the batch (atomicMax(~i)), the commit tombstones the slot for the
-// elected item and clears the word.
-__device__ __forceinline__ void unreg_find_elect_item(uint32_t i, const gd_key* __restrict__ keys,
-                                                      const uint32_t* __restrict__ acts, const Slot* slots,
-                                                      unsigned long long mask, const DevCounters* ctr,
-                                                      uint32_t* __restrict__ slot_of, uint32_t* __restrict__ last) {
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
-    uint32_t res = NONE32;
-    for (uint32_t p = 0; p <= ctr->max_probe; ++p) {
-        const uint4* q = reinterpret_cast<const uint4*>(slots + s);
-        const uint4 a = q[0], b = q[1];
-        const uint32_t st = slot_state(b.w);
-        if (st == SLOT_EMPTY) break;
-        if (st == SLOT_LIVE && ((uint64_t)a.x | ((uint64_t)a.y << 32)) == n0 &&
-            ((uint64_t)a.z | ((uint64_t)a.w << 32)) == n1 && ((uint64_t)b.x | ((uint64_t)b.y << 32)) == tcd) {
-            if (b.z == acts[i]) res = (uint32_t)s;
-            break;
-        }
-        s = (s + 1) & mask;
-    }
-    slot_of[i] = res;
-    if (res != NONE32) atomicMax(&last[res], ~i);
-}
-static __global__ void __launch_bounds__(BLOCK) k_unreg_find_elect(const gd_key* __restrict__ keys,
-                                                            const uint32_t* __restrict__ acts, uint32_t n,
-                                                            const Slot* slots, unsigned long long mask,
-                                                            const DevCounters* ctr, uint32_t* __restrict__ slot_of,
-                                                            uint32_t* __restrict__ last) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < n) unreg_find_elect_item(i, keys, acts, slots, mask, ctr, slot_of, last);
-}
-__device__ __forceinline__ bool unreg_elected_commit(uint32_t i, uint32_t n, const uint32_t* __restrict__ slot_of,
-                                                     Slot* slots, uint32_t* __restrict__ last,
-                                                     uint8_t* __restrict__ out_removed) {
-    if (i >= n) return false;
-    const uint32_t s = slot_of[i];
-    const bool rm = s != NONE32 && last[s] == ~i;
-    if (rm) {
-        slots[s].meta = make_meta(SLOT_TOMB, 0);
-        last[s] = 0;
-    }
-    if (out_removed) out_removed[i] = rm ? 1 : 0;
-    return rm;
-}
-static __global__ void __launch_bounds__(BLOCK) k_unreg_commit_elect(const uint32_t* __restrict__ slot_of, uint32_t n,
-                                                              Slot* slots, DevCounters* ctr,
-                                                              uint32_t* __restrict__ last,
-                                                              uint8_t* __restrict__ out_removed) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    live_delta(ctr, unreg_elected_commit(i, n, slot_of, slots, last, out_removed), true);
-}
-
-// The matched entry is being removed, so its n0 word can carry the election.
-static __global__ void __launch_bounds__(BLOCK) k_unreg_poison(const uint32_t* __restrict__ slot_of, uint32_t n, Slot* slots) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n || slot_of[i] == NONE32) return;
-    slots[slot_of[i]].n0 = ~0ull;
-}
-
-static __global__ void __launch_bounds__(BLOCK) k_unreg_min(const uint32_t* __restrict__ slot_of, uint32_t n, Slot* slots) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n || slot_of[i] == NONE32) return;
-    atomicMin(reinterpret_cast<unsigned long long*>(&slots[slot_of[i]].n0), (unsigned long long)i);
-}
-
-__device__ __forceinline__ bool unreg_commit_item(uint32_t i, const uint32_t* __restrict__ slot_of, Slot* slots,
-                                                  DevCounters* ctr, uint8_t* __restrict__ out_removed) {
-    const uint32_t s = slot_of[i];
-    uint8_t removed = 0;
-    if (s != NONE32 && slots[s].n0 == (uint64_t)i) {
-        slots[s].meta = make_meta(SLOT_TOMB, 0);       // live - 1, tomb + 1: the kernel's live_delta
-        removed = 1;
-    }
-    if (out_removed) out_removed[i] = removed;
-    return removed != 0;
-}
-static __global__ void __launch_bounds__(BLOCK) k_unreg_commit(const uint32_t* __restrict__ slot_of, uint32_t n,
-                                                        Slot* slots, DevCounters* ctr,
-                                                        uint8_t* __restrict__ out_removed) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    const bool rm = i < n && unreg_commit_item(i, slot_of, slots, ctr, out_removed);
-    live_delta(ctr, rm, true);
-}
-
-static __global__ void __launch_bounds__(BLOCK) k_dir_lookup(const gd_key* __restrict__ keys, uint32_t n, TableArgs tab,
-                                                      gd_val* __restrict__ out_vals, uint8_t* __restrict__ found) {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    uint32_t act, meta;
-    const bool hit = probe(tab.slots, tab.mask, tab.ctr->max_probe, uniform_hash(n0, n1, tcd), n0, n1, tcd, act, meta);
-    out_vals[i] = hit ? gd_val{act, slot_silo(meta)} : gd_val{NONE32, NONE32};
-    found[i] = hit ? 1 : 0;
-}
-
-// Rebuild: every live entry of the old table into the new one (keys are distinct,
-// so a claimer never needs to compare keys).
-static __global__ void __launch_bounds__(BLOCK) k_rehash(const Slot* __restrict__ old_slots, unsigned long long old_cap,
-                                                  Slot* slots, unsigned long long mask, DevCounters* ctr,
-                                                  const uint32_t* __restrict__ old_vtag, uint32_t* __restrict__ vtag) {
-    const unsigned long long j = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    uint32_t pd = 0;
-    bool placed = false;
-    const Slot sl = j < old_cap ? old_slots[j] : Slot{};
-    if (j < old_cap && slot_state(sl.meta) == SLOT_LIVE) {
-        unsigned long long s = home_slot(uniform_hash(sl.n0, sl.n1, sl.tcd), mask);
-        for (uint32_t dist = 0; dist <= mask; ++dist) {
-            uint32_t expected = make_meta(SLOT_EMPTY, 0);
-            if (__hip_atomic_compare_exchange_strong(&slots[s].meta, &expected, make_meta(SLOT_CLAIMED, 0),
-                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                slots[s].n0 = sl.n0;
-                slots[s].n1 = sl.n1;
-                slots[s].tcd = sl.tcd;
-                slots[s].act = sl.act;
-                if (vtag) vtag[s] = old_vtag[j];
-                __hip_atomic_store(&slots[s].meta, sl.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pd = dist;
-                placed = true;
-                break;
-            }
-            s = (s + 1) & mask;
-        }
-        if (!placed) atomicOr(&ctr->err, 2u);
-    }
-    // one max_probe / live update a wave (one an entry queued 10^6 same-address atomics at cfg 2)
-    claim_counters(ctr, pd, false);
-    live_delta(ctr, placed, false);
 }
 
 // ------------------------------------------------------------------ wave helpers
