@@ -117,6 +117,7 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->cx_heap);
     free_buf(h->cxi_tab);
     free_buf(h->cx8_tab);
+    free_buf(h->cxd_tab);
     free_buf(h->reg_retry);
     for (auto& d : h->dir_scr) free_buf(d);
     free_buf(h->cxi_types);

@@ -187,6 +187,7 @@ bool cx_current(const gd_handle* h) {
 TabTrack::TabTrack(gd_handle* hh) : h(hh), was_current(cx_current(hh)) {
     ++h->tab_track;
     h->cx8_pure = false;                 // until a read-back after the batch shows the index still pure
+    h->cx_snap++;                        // the direct table, if any, is stale from here on
 }
 
 static uint32_t bit_len(uint64_t x) {
@@ -272,6 +273,7 @@ static int cx_build(gd_handle* h) {
     h->cx_out8_at = h->cx_ctr_host.out8;              // the build's own: the baseline of the rebuild rule
     h->cx8_pure = h->cx8_ok && h->cx8_layout.ntypes == 1 && h->cx_ctr_host.out8 == 0;
     h->cx_builds++;
+    h->cx_snap++;                                     // the 8-B index was re-laid
     h->cx_build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return GD_OK;
 }
@@ -457,13 +459,65 @@ int bucket_sub(uint64_t n, uint32_t n_act) {
     return per_range;
 }
 
+#if GD_DIRECT_INDEX
+// The direct table for a route that took variant `var` (cx: the indexes are current): *use when the route
+// may read it, *d its arguments.  Eligible while the 8-B index is pure, the table is at most half the
+// 8-B index's bytes and d <= 2^30; d comes from CxCounters::n1_max of the read-back that showed the index
+// pure.  A table built under another snapshot id is never read: the route takes the PURE or general form
+// in that same call.  Built (a memset and k_cxd_build on the route's stream, right before the route --
+// the stream order the PURE form rests on) only when the previous k_route launch on this handle found the
+// index pure under the same snapshot id: a directory that changes between routes never pays for it.
+static int cxd_prepare(gd_handle* h, bool cx, int var, bool* use, CxdArgs* d) {
+    *use = false;
+    const bool pure = cx && h->cx8_pure;
+    const uint64_t snap = h->cx_snap + h->tab_gen;
+    const bool quiet = pure && h->cxd_seen && h->cxd_seen_snap == snap;
+    h->cxd_seen = pure;
+    h->cxd_seen_snap = snap;
+    if (!pure || var != 3) return GD_OK;
+    const uint64_t dd = ((uint64_t)h->cx_ctr_host.n1_max + 1 + 15) & ~15ull;
+    if (dd * 4 > (uint64_t)h->capacity * 8 / 2 || dd > (1ull << 30)) {
+        if (h->cxd_ok) h->cx_snap++;                  // no longer eligible
+        h->cxd_ok = false;
+        return GD_OK;
+    }
+    if (!(h->cxd_ok && h->cxd_snap_at == snap && h->cxd_d == dd)) {
+        h->cxd_ok = false;
+        if (!quiet) return GD_OK;
+        GD_TRY(ensure_own(h, h->cxd_tab, dd * 4));    // kept while d fits
+        HIP_TRY(h, hipMemsetAsync(h->cxd_tab.p, 0, dd * 4, h->stream));
+        const uint32_t g = std::max<uint32_t>(1, std::min<uint64_t>(blocks_for(h->capacity, BLOCK), (uint64_t)h->n_cu * 16));
+        GD_TRY(launch(h, "k_cxd_build", dim3(g), dim3(BLOCK), 0, k_cxd_build, (const unsigned long long*)h->cx8_tab.p,
+                      (unsigned long long)h->capacity, (uint32_t*)h->cxd_tab.p, (uint32_t)dd));
+        h->cxd_ok = true;
+        h->cxd_d = (uint32_t)dd;
+        h->cxd_snap_at = snap;
+        h->cxd_builds++;
+    }
+    *use = true;
+    *d = CxdArgs{(const uint32_t*)h->cxd_tab.p, h->cxd_d, h->cx8_layout.ab, h->cx8_layout.sb, h->cx8_layout.tcd[0]};
+    return GD_OK;
+}
+#endif
+
 template <int MODE, int M, bool NT>
 int route_launch(gd_handle* h, const gd_key* keys, uint32_t n, uint32_t* silo, uint32_t* act, uint8_t* status) {
     bool cx = false;
     GD_TRY(cx_ensure(h, &cx, n));
     int meas = -1;
     const int var = cx ? cx_choose(h, 0, n, &meas, h->cx8_ok ? 4 : 3) : 1;
+#if GD_DIRECT_INDEX
+    bool direct = false;
+    CxdArgs cxd{};
+    GD_TRY(cxd_prepare(h, cx, var, &direct, &cxd));  // a build is not part of the variant's timing
+#endif
     CxMeasure m(h, meas, n);
+#if GD_DIRECT_INDEX
+    if (direct)
+        return launch(h, "k_route", dim3(blocks_for(n, BLOCK * M)), dim3(BLOCK), ring_lds(h),
+                      k_route_d<MODE, M, NT, 0>, keys, n, ring_args(h), table_args(h), silo, act, status,
+                      0ull, h->route_xcd ? 1u : 0u, (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, cxd);
+#endif
     if (var == 3 && h->cx8_pure)             // nothing to fall back to the directory for (gd_engine.h cx8_pure)
         return launch(h, "k_route", dim3(blocks_for(n, BLOCK * M)), dim3(BLOCK), ring_lds(h),
                       k_route_m<MODE, M, NT, 0, false, (int)CX_GROUP, true, true>, keys, n, ring_args(h),
@@ -501,10 +555,29 @@ int route_n1_mode(gd_handle* h, const gd_key* k, uint32_t n1w, uint64_t tcd, uin
     GD_TRY(cx_ensure(h, &cx, n));
     int meas = -1;
     const int var = cx ? cx_choose(h, 1, n, &meas, h->cx8_ok ? 4 : 3) : 1;
+#if GD_DIRECT_INDEX
+    bool direct = false;
+    CxdArgs cxd{};
+    GD_TRY(cxd_prepare(h, cx, var, &direct, &cxd));
+#endif
     CxMeasure m(h, meas, n);
     // the N1 stream non-temporal under route_mode's rule (world-1 exchange pipeline: 0.5791 -> 0.5773 ms,
     // profiles/r05_route_n1_nt_ab.txt)
     const bool nt = (uint64_t)h->capacity * 8u <= ROUTE_NT_INDEX_BYTES;
+#if GD_DIRECT_INDEX
+    if (direct && nt && n1w == 4)
+        return launch(h, "k_route", g, b, ring_lds(h), k_route_d<MODE, 1, true, 4>, k, n, ring_args(h),
+                      table_args(h), silo, act, status, tcd, xcd, rcnt, world, src, cxd);
+    if (direct && nt)
+        return launch(h, "k_route", g, b, ring_lds(h), k_route_d<MODE, 1, true, 8>, k, n, ring_args(h),
+                      table_args(h), silo, act, status, tcd, xcd, rcnt, world, src, cxd);
+    if (direct && n1w == 4)
+        return launch(h, "k_route", g, b, ring_lds(h), k_route_d<MODE, 1, false, 4>, k, n, ring_args(h),
+                      table_args(h), silo, act, status, tcd, xcd, rcnt, world, src, cxd);
+    if (direct)
+        return launch(h, "k_route", g, b, ring_lds(h), k_route_d<MODE, 1, false, 8>, k, n, ring_args(h),
+                      table_args(h), silo, act, status, tcd, xcd, rcnt, world, src, cxd);
+#endif
     if (var == 3 && nt && n1w == 4)
         return launch(h, "k_route", g, b, ring_lds(h), k_route_m<MODE, 1, true, 4, false, (int)CX_GROUP, true>, k, n,
                       ring_args(h), table_args(h), silo, act, status, tcd, xcd, rcnt, world, src, CxArgs{},

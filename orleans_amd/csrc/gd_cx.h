@@ -6,13 +6,15 @@
 //   k_cx_types    one pass over the table: the set of distinct TypeCodeData of N0 = 0 entries with a
 //                 count each (per-workgroup LDS sets, one global insert per type and workgroup), the
 //                 largest activation and silo, the entries no index can hold (N0 != 0) and those the
-//                 8-B index cannot (N1 >= 2^32).  The host picks the 8-B layout from them.
+//                 8-B index cannot (N1 >= 2^32), the largest N1 below 2^32.  The host picks the 8-B layout
+//                 (and the direct table's size) from them.
 //   k_cx_project  one streaming pass: every table slot -> its 16-B and 8-B index slots (the full build).
 //   k_cx_sync     the slots one directory batch touched (register, upsert, unregister) re-projected
 //                 in place: the directory change costs a pass over the batch, not over the table
 //                 (GrainDirectoryPartition.AddSingleActivation / RemoveActivation are O(1) dictionary
 //                 operations, GrainDirectoryPartition.cs:304-363, and activations register all the
 //                 time, Catalog.cs:540-552).
+//   k_cxd_build   the direct table (gd_kernels.h CxdArgs) from a pure 8-B index: one pass over its slots.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,7 +36,9 @@ struct CxCounters {
     uint32_t act_max;      // the largest activation (GD_ACT_MULTI aside) and silo: the host's bit split
     uint32_t silo_max;
     uint32_t out8;         // projections (build and sync) the 8-B index does not hold or redirects
-    uint32_t pad[2];
+    uint32_t n1_max;       // the largest N1 of the N0 = 0, N1 < 2^32 entries seen live (k_cx_types, then every
+                           // projection of a batch; removals leave it): the direct table's size
+    uint32_t pad[1];
 };
 
 // ---- type sets ------------------------------------------------------------------
@@ -81,13 +85,13 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_types(const Slot* __restric
                                                     unsigned long long* types, uint32_t* count, CxCounters* ctr) {
     __shared__ unsigned long long s_t[CXT_LDS];
     __shared__ uint32_t s_c[CXT_LDS];
-    __shared__ uint32_t s_red[4][BLOCK / WAVE];
+    __shared__ uint32_t s_red[5][BLOCK / WAVE];
     for (uint32_t k = threadIdx.x; k < CXT_LDS; k += BLOCK) {
         s_t[k] = CX_NO_TYPE;
         s_c[k] = 0;
     }
     __syncthreads();
-    uint32_t n0c = 0, bigc = 0, amax = 0, smax = 0, run_c = 0;
+    uint32_t n0c = 0, bigc = 0, amax = 0, smax = 0, nmax = 0, run_c = 0;
     unsigned long long run_t = CX_NO_TYPE;
     const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK * CXT_IT;
     for (unsigned long long base = (unsigned long long)blockIdx.x * BLOCK * CXT_IT + threadIdx.x; base < cap;
@@ -111,6 +115,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_types(const Slot* __restric
                 continue;
             }
             if (a[r].w != 0) ++bigc;
+            else nmax = max(nmax, a[r].z);
             if (b[r].z != GD_ACT_MULTI) amax = max(amax, b[r].z);
             smax = max(smax, slot_silo(b[r].w));
             const unsigned long long tcd = (unsigned long long)b[r].x | ((unsigned long long)b[r].y << 32);
@@ -129,6 +134,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_types(const Slot* __restric
         bigc += __shfl_xor(bigc, off, WAVE);
         amax = max(amax, (uint32_t)__shfl_xor(amax, off, WAVE));
         smax = max(smax, (uint32_t)__shfl_xor(smax, off, WAVE));
+        nmax = max(nmax, (uint32_t)__shfl_xor(nmax, off, WAVE));
     }
     const uint32_t w = threadIdx.x / WAVE;
     if ((threadIdx.x & (WAVE - 1)) == 0) {
@@ -136,6 +142,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_types(const Slot* __restric
         s_red[1][w] = bigc;
         s_red[2][w] = amax;
         s_red[3][w] = smax;
+        s_red[4][w] = nmax;
     }
     __syncthreads();                                   // also: every cx_type_note of the workgroup is done
     if (threadIdx.x == 0) {
@@ -144,11 +151,13 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_types(const Slot* __restric
             bigc += s_red[1][k];
             amax = max(amax, s_red[2][k]);
             smax = max(smax, s_red[3][k]);
+            nmax = max(nmax, s_red[4][k]);
         }
         if (n0c) atomicAdd(&ctr->n0_live, n0c);
         if (bigc) atomicAdd(&ctr->big_n1, bigc);
         if (amax) atomicMax(&ctr->act_max, amax);
         if (smax) atomicMax(&ctr->silo_max, smax);
+        if (nmax) atomicMax(&ctr->n1_max, nmax);
     }
     for (uint32_t k = threadIdx.x; k < CXT_LDS; k += BLOCK)
         if (s_t[k] != CX_NO_TYPE) (void)cx_type_add(types, count, s_t[k], s_c[k], ctr);
@@ -170,8 +179,10 @@ __device__ __forceinline__ void cx_stage_types(const unsigned long long* types, 
 // Table slot j (a, b: its two halves) -> index slot j.  add_types (k_cx_sync): a type the staged set
 // lacks is looked up / inserted in the global set (a batch may register a new grain class).
 // Returns whether the 8-B index holds the entry (false for a live entry it does not hold or redirects).
+// nctr (a batch's projections): n1_max follows an entry the 8-B index holds (rarely past it: one load).
 __device__ __forceinline__ bool cx_project(const uint4 a, const uint4 b, unsigned long long j, const CxBuild& B,
-                                           const unsigned long long* s_types, bool add_types) {
+                                           const unsigned long long* s_types, bool add_types,
+                                           CxCounters* nctr = nullptr) {
     const uint32_t st = slot_state(b.w);
     uint4 v16 = make_uint4(0, 0, 0, 0);
     unsigned long long v8 = 0;
@@ -200,6 +211,10 @@ __device__ __forceinline__ bool cx_project(const uint4 a, const uint4 b, unsigne
                 if (act != GD_ACT_MULTI && act >= am - 1u) av = am - 1u;   // redirect: activation too wide
                 held8 = u != umax && av != am - 1u;
                 v8 = ((unsigned long long)((u << ab) | av) << 32) | a.z;
+#if GD_DIRECT_INDEX
+                if (nctr && a.z > __hip_atomic_load(&nctr->n1_max, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+                    atomicMax(&nctr->n1_max, a.z);
+#endif
             }
         }
     } else if (st != SLOT_EMPTY) {
@@ -240,6 +255,22 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_project(const Slot* __restr
     if ((threadIdx.x & (WAVE - 1)) == 0 && out8) atomicAdd(&ctr->out8, out8);
 }
 
+#if GD_DIRECT_INDEX
+// The direct table from a pure 8-B index (cleared before): every slot that holds an entry (y > 1: not empty,
+// not a hole) stores its payload word at its key word.  Pure: one class, so key words are distinct; d
+// bounds them (CxCounters::n1_max of the same read-back), checked all the same.
+static __global__ void __launch_bounds__(BLOCK) k_cxd_build(const unsigned long long* __restrict__ cx8,
+                                                     unsigned long long cap, uint32_t* __restrict__ tab,
+                                                     uint32_t d) {
+    const unsigned long long stride = (unsigned long long)gridDim.x * BLOCK;
+    for (unsigned long long j = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x; j < cap; j += stride) {
+        const unsigned long long v = cx8[j];
+        const uint32_t x = (uint32_t)v, y = (uint32_t)(v >> 32);
+        if (y > 1u && x < d) tab[x] = y;
+    }
+}
+#endif
+
 // Incremental: the table slots a directory batch touched (slot_of[i]; NONE32 / SLOT_RETRY: none),
 // re-projected after the batch's last table write.  Duplicates are harmless (a projection is a function
 // of the table slot).
@@ -253,7 +284,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cx_sync(const uint32_t* __rest
         const uint32_t s = slot_of[i];
         if (s < SLOT_RETRY) {
             const uint4* q = reinterpret_cast<const uint4*>(slots + s);
-            out = !cx_project(q[0], q[1], s, B, s_types, true);
+            out = !cx_project(q[0], q[1], s, B, s_types, true, ctr);
         }
     }
     const unsigned long long m = __ballot(out);
@@ -287,7 +318,7 @@ static __global__ void __launch_bounds__(BLOCK) k_reg_commit_elect_cx(const uint
         reg_commit_item(i, slot_of, vals, slots, ctr, vtag, op);
         const uint32_t s = slot_of[i];
         const uint4* q = reinterpret_cast<const uint4*>(slots + s);
-        out = !cx_project(q[0], q[1], s, B, s_types, true);
+        out = !cx_project(q[0], q[1], s, B, s_types, true, cctr);
     }
     const unsigned long long m = __ballot(out);
     if (lane_id() == 0 && m) atomicAdd(&cctr->out8, (uint32_t)__popcll(m));

@@ -237,6 +237,18 @@ struct gd_handle {
     bool cx8_pure = false;
     Cx8Args cx8_layout{};       // its layout (types, bits), fixed at the build
     DevBuf cx8_tab;
+    // the direct table standing in for a pure 8-B index over dense N1s (gd_kernels.h CxdArgs, eng_core.hip
+    // cxd_prepare).  cx_snap + tab_gen is the directory's snapshot id: every path that clears cx8_pure or
+    // rebuilds / re-lays the 8-B index advances one of the two.  The table is read only under the id it was
+    // built at, and built only when the previous k_route launch found the index pure under the same id.
+    DevBuf cxd_tab;
+    uint64_t cx_snap = 0;
+    bool cxd_ok = false;
+    uint32_t cxd_d = 0;                          // its entries
+    uint64_t cxd_snap_at = 0;                    // the snapshot id it was built at
+    bool cxd_seen = false;                       // the previous k_route launch found the index pure ...
+    uint64_t cxd_seen_snap = 0;                  // ... under this snapshot id
+    uint64_t cxd_builds = 0;
     CxCounters cx_ctr_host{};   // the last read-back of the index counters
     uint32_t cx_out8_at = 0, cx_held8_at = 0;   // at the build: live entries the 8-B index left out / held
     uint64_t cx_builds = 0, cx_synced = 0;      // full builds; slots re-projected by k_cx_sync (gd_stats)

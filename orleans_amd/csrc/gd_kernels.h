@@ -243,6 +243,20 @@ __device__ __forceinline__ int cx8_type(const Cx8Args& c, uint64_t n0, uint64_t 
     return t;
 }
 
+//   Direct table (GD_DIRECT_INDEX, gd_cx.h k_cxd_build): while the 8-B index is pure (one grain class, N0 = 0,
+//   N1 < 2^32, every live entry held, none redirected) an entry's identity is its low N1 word, so dense
+//   N1s are indexed directly: tab[N1] = the 8-B slot's payload word y (same ab / sb), 0 = empty.  No key
+//   word, no hash, no probe chain: the array position is the key.
+#ifndef GD_DIRECT_INDEX
+#define GD_DIRECT_INDEX 1
+#endif
+struct CxdArgs {
+    const uint32_t* tab;           // d entries
+    uint32_t d;                    // (largest live N1 + 1) rounded up to 16
+    uint32_t ab, sb;               // the 8-B index's bit split
+    uint64_t tcd;                  // its one grain class
+};
+
 // Directory entry -> route result (LookUpActivations + IsValidSilo + the single-activation choice).
 __device__ __forceinline__ void entry_result(const TableArgs& tab, uint32_t a, uint32_t silo_of, uint32_t& silo,
                                              uint32_t& act, uint8_t& status) {
@@ -255,6 +269,13 @@ __device__ __forceinline__ void entry_result(const TableArgs& tab, uint32_t a, u
     } else {
         status = GD_ROUTE_MISS;                    // IsValidSilo filtered it (GrainDirectoryPartition.cs:431)
     }
+}
+
+// An 8-B index payload word y of an entry the index holds (no redirect) -> route result.
+__device__ __forceinline__ void cx8_decode(uint32_t ab, uint32_t sb, const TableArgs& tab, uint32_t y, uint32_t& silo,
+                                           uint32_t& act, uint8_t& status) {
+    const uint32_t am = (1u << ab) - 1u, u = y >> ab, a = y & am;
+    entry_result(tab, a == am ? GD_ACT_MULTI : a, (u & ((1u << sb) - 1u)) - 1u, silo, act, status);
 }
 
 // The table's max_probe, read when a walk first leaves its home group (rare): kernels on the index do not
@@ -333,7 +354,7 @@ __device__ __forceinline__ bool cx8_walk(const Cx8Args& c, const TableArgs& tab,
     if (hit == 0) return false;
     const uint32_t am = (1u << c.ab) - 1u, u = hit >> c.ab, a = hit & am;
     if (u == umax || a == am - 1u) return true;                         // redirect: the directory answers
-    entry_result(tab, a == am ? GD_ACT_MULTI : a, (u & ((1u << c.sb) - 1u)) - 1u, silo, act, status);
+    cx8_decode(c.ab, c.sb, tab, hit, silo, act, status);
     return false;
 }
 
@@ -367,9 +388,7 @@ __device__ __forceinline__ void cx8_walk_pure(const Cx8Args& c, const TableArgs&
 #pragma unroll
         for (int k = 0; k < (int)CX8_GROUP / 2; ++k) q[k] = qp[k];
     }
-    if (hit == 0) return;
-    const uint32_t am = (1u << c.ab) - 1u, u = hit >> c.ab, a = hit & am;
-    entry_result(tab, a == am ? GD_ACT_MULTI : a, (u & ((1u << c.sb) - 1u)) - 1u, silo, act, status);
+    if (hit != 0) cx8_decode(c.ab, c.sb, tab, hit, silo, act, status);
 }
 
 // Linear probe of the open-addressing directory for a live entry with this key.
@@ -763,6 +782,103 @@ static __global__ void __launch_bounds__(BLOCK) k_route_m(const gd_key* __restri
         }
     }
 }
+
+#if GD_DIRECT_INDEX
+// k_route_m's DIRECT form (launched as "k_route"): the pure 8-B index stood in for by the direct table
+// (CxdArgs).  A lane whose key passes the PURE path's class checks and has N1 < d reads tab[N1] with one
+// 4-B temporal load; a non-zero word is the entry (cx8_decode: GD_ACT_MULTI, IsValidSilo at route time).
+// Only the lanes that do not end GD_ROUTE_OK -- N0 != 0, another class, N1 >= d, an empty word, an
+// invalid silo, several activations -- compute the Jenkins hash and search the ring, for the owner silo
+// the other forms report with those statuses; a hit needs neither.  Key stream, silo / status stores and
+// XCD ranges as k_route_m's; act stays a temporal store and M follows route_mode (both measured,
+// profiles/r07_direct_index_ab.json).
+template <int MODE, int M, bool NT, int N1W>
+static __global__ void __launch_bounds__(BLOCK) k_route_d(const gd_key* __restrict__ keys, uint32_t n, RingArgs ring,
+                                                   TableArgs tab, uint32_t* __restrict__ out_silo,
+                                                   uint32_t* __restrict__ out_act,
+                                                   uint8_t* __restrict__ out_status, uint64_t tcd_u, uint32_t xcd,
+                                                   const uint32_t* __restrict__ rcnt, uint32_t world,
+                                                   uint32_t* __restrict__ src_out, CxdArgs d) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t s_ring[];
+    __shared__ uint32_t s_soff[257];
+    uint32_t* s_pts = s_ring;
+    uint32_t* s_own = s_ring + ring.n;
+    if (src_out && threadIdx.x == 0) {
+        uint32_t run = 0;
+        for (uint32_t q = 0; q < world; ++q) {
+            s_soff[q] = run;
+            run += rcnt[q];
+        }
+        s_soff[world] = run;
+    }
+    stage_ring(ring, s_pts, s_own);                    // its barrier publishes s_soff too
+    const uint32_t base = xcd_tile(blockIdx.x, gridDim.x, xcd) * (BLOCK * M) + threadIdx.x;
+    uint64_t n0[M], n1[M], tcd[M];
+    uint32_t y[M];
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const uint32_t i = base + j * BLOCK;
+        n0[j] = n1[j] = tcd[j] = 0;
+        if (i < n) {
+            if constexpr (N1W == 8) {
+                n1[j] = ld<NT>(reinterpret_cast<const uint64_t*>(keys) + i);
+                tcd[j] = tcd_u;
+            } else if constexpr (N1W == 4) {
+                n1[j] = ld<NT>(reinterpret_cast<const uint32_t*>(keys) + i);
+                tcd[j] = tcd_u;
+            } else {
+                const uint64_t* kp = reinterpret_cast<const uint64_t*>(keys + i);
+                n0[j] = ld<NT>(kp);
+                n1[j] = ld<NT>(kp + 1);
+                tcd[j] = ld<NT>(kp + 2);
+            }
+        }
+    }
+    // every message's table word in flight before any is decoded (the special categories below never
+    // look at theirs)
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const bool in = base + j * BLOCK < n && n0[j] == 0 && tcd[j] == d.tcd && n1[j] < (uint64_t)d.d;
+        y[j] = in ? d.tab[(uint32_t)n1[j]] : 0u;
+    }
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        const uint32_t i = base + j * BLOCK;
+        if (i >= n) continue;
+        const uint32_t cat = (uint32_t)(tcd[j] >> 56);
+        uint32_t silo, act = NONE32;
+        uint8_t status;
+        if (cat == CAT_SYSTEM_TARGET) {                        // LocalGrainDirectory.cs:480-485
+            silo = ring.my_silo;
+            status = GD_ROUTE_SYSTEM_TARGET;
+        } else if (is_membership(n0[j], n1[j], tcd[j])) {     // :487-503
+            silo = ring.seed_silo;
+            status = GD_ROUTE_MEMBERSHIP;
+        } else if (cat == CAT_KEYEXT_GRAIN || cat == CAT_GEO_CLIENT) {  // UniqueKey.cs:279-281
+            silo = NONE32;
+            status = GD_ROUTE_KEYEXT;
+        } else {
+            silo = 0;
+            status = GD_ROUTE_MISS;
+            if (y[j] != 0) cx8_decode(d.ab, d.sb, tab, y[j], silo, act, status);
+            if (status != GD_ROUTE_OK)                         // the owner silo: hash and ring search, these lanes only
+                silo = s_own[ring_position<MODE>(s_pts, ring.n, ring.top, uniform_hash(n0[j], n1[j], tcd[j]))];
+        }
+        st<true>(out_silo + i, silo);                          // silo / status: not read again on the device
+        out_act[i] = act;                                      // act: the bucketing's input, next (temporal)
+        st<true>(out_status + i, status);
+        if (src_out) {
+            uint32_t lo = 0, hi = world;                       // largest q with s_soff[q] <= i
+            while (hi - lo > 1) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (s_soff[mid] <= i) lo = mid;
+                else hi = mid;
+            }
+            st<true>(src_out + i, lo);
+        }
+    }
+}
+#endif  // GD_DIRECT_INDEX
 
 // The route's memory bound (gd_route_bound_device, a diagnostic, not a route): k_route_m<…, CX8>'s XCD
 // mapping, ring-sized LDS, key reads, home hash, one 64-B group read of the 8-B index per message and

@@ -8,7 +8,8 @@ roofline reads its `traffic` (load_pmc).
 
 <kernel> is the library's launch name (the names of bench.py's `kernels`), not the template function:
 k_b2_hist / k_radix_hist16 are launched as k_radix_hist, k_b2_scatter as k_radix_scatter,
-k_msd_local_list<512, ...> as k_msd_local_mid and <1024, ...> as k_msd_local, k_route_m as k_route.
+k_msd_local_list<512, ...> as k_msd_local_mid and <1024, ...> as k_msd_local, k_route_m and its DIRECT form
+k_route_d as k_route (k_cxd_build, the direct table's build, keeps its own name).
 Instantiations of one launch name are averaged weighted by their calls; instantiations with under a
 quarter of the busiest one's calls (variants the tuner timed and dropped) are left out.
 
@@ -26,7 +27,8 @@ import sys
 
 RENAME = {"k_b2_hist": "k_radix_hist", "k_radix_hist16": "k_radix_hist", "k_radix_hist_multi": "k_radix_hist",
           "k_b2_scatter": "k_radix_scatter",
-          "k_route_m": "k_route", "k_route_region": "k_route", "k_shard_gather": "k_shard_scatter",
+          "k_route_m": "k_route", "k_route_d": "k_route", "k_route_region": "k_route",
+          "k_shard_gather": "k_shard_scatter",
           "k_fill_u32": "k_fill", "k_fan_degree_tiles": "k_fan_degree"}
 GATHER = ("k_route", "k_fan_route")
 
