@@ -889,6 +889,62 @@ int gd_receive_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const 
                       uint32_t n_ctx, const gd_recv_limits* limits, const gd_frame_fields* out, uint32_t* out_ctx,
                       uint8_t* out_status, uint32_t* out_perm, uint32_t* out_offsets);
 
+/* ---- sender queues ------------------------------------------------
+ * OutboundMessageQueue.SendMessage (OutboundMessageQueue.cs:54-131) for a batch that Dispatcher.
+ * AddressMessage (gd_route) has addressed: which sender queue every message goes on, and the batch as
+ * one contiguous, ordered index list per queue.  Per message, in the reference's order:
+ *   GD_SEND_HELD          route status given and none of GD_ROUTE_OK / _SYSTEM_TARGET / _MEMBERSHIP: the
+ *                         message has no address yet (slow path, KeyExt, multi-activation, undecoded)
+ *   GD_SEND_EXPIRED       ttl != GD_TTL_NONE and ttl <= 0 (Message.IsExpired, Message.cs:293-302; ttl =
+ *                         TimeToLive in TimeSpan ticks when the batch is sent): dropped
+ *   GD_SEND_NO_SILO       silo == GD_NO_SILO (:82-87): rejection, Unrecoverable
+ *   GD_SEND_UNKNOWN_SILO  silo >= n_silos: not in the configured silo table
+ *   GD_SEND_LOOPBACK      silo == gd_config.my_silo (:90-95): bucket 0, InboundQueue.PostMessage
+ *   GD_SEND_QUEUED        category 0 (Ping, Message.cs:75-80): bucket 1, the ping sender; category 1
+ *                         (System): bucket 2, the system sender; any other byte (the C# default: branch,
+ *                         Application = 2): bucket 3 + Math.Abs(silo_hash[silo]) % n_queues (:125)
+ *   GD_SEND_THROWS        ... unless silo_hash[silo] == INT32_MIN, whose Math.Abs throws
+ *                         OverflowException (checked before the modulo, as in .NET)
+ * Everything but LOOPBACK and QUEUED lands in the trailing bucket 3 + n_queues, told apart by status.
+ * category NULL = every message Application; ttl NULL = no message has a TTL; route status NULL =
+ * nothing is held.  out_queue[i] = the bucket id; perm[n] = the message indices grouped by bucket, each
+ * bucket in batch order (every sender is a FIFO, SiloMessageSender.QueueRequest); offsets[n_queues + 5]
+ * = the bucket starts, offsets[n_queues + 4] = n.  out_queue, and perm + offsets together, may be NULL
+ * (perm + offsets NULL: classification only); one of perm / offsets without the other is GD_EINVAL.
+ * n == 0 is valid and fills offsets with zeros.  n <= 2^31.
+ * gd_send_configure: silo_hash[s] = gd_silo_consistent_hash of silo index s (host pointer), 1 <= n_silos
+ * <= 65,536, 1 <= n_queues <= 1,024 (SiloMessagingOptions.SiloSenderQueues), else GD_EINVAL; may be
+ * called again (the silo table grows); synchronizes the handle.  The batch calls return GD_ESTATE before
+ * it (a NULL handle has no configuration: GD_ESTATE too, after the argument checks).
+ * Left to C#: the stopped flag (:58-62), QueuedTime, the gateway proxy check (:77), the ShouldDrop test
+ * hook, and MessageCenter.SendMessage's IsBlockingApplicationMessages filter (MessageCenter.cs:177-191). */
+#define GD_TTL_NONE INT64_MAX           /* TimeToLive has no value */
+#define GD_SEND_QUEUED       0
+#define GD_SEND_LOOPBACK     1
+#define GD_SEND_EXPIRED      2
+#define GD_SEND_NO_SILO      3
+#define GD_SEND_UNKNOWN_SILO 4
+#define GD_SEND_THROWS       5
+#define GD_SEND_HELD         6
+int gd_send_configure(gd_handle* h, const int32_t* silo_hash, uint32_t n_silos, uint32_t n_queues);
+int gd_send_queues_device(gd_handle* h, const uint32_t* d_silo, const uint8_t* d_route_status,
+                          const uint8_t* d_category, const int64_t* d_ttl, uint32_t n, uint8_t* d_send_status,
+                          uint32_t* d_queue, uint32_t* d_perm, uint32_t* d_offsets);
+/* Host pointers, synchronous. */
+int gd_send_queues(gd_handle* h, const uint32_t* silo, const uint8_t* route_status, const uint8_t* category,
+                   const int64_t* ttl, uint32_t n, uint8_t* out_send_status, uint32_t* out_queue,
+                   uint32_t* out_perm, uint32_t* out_offsets);
+/* Dispatcher.AddressMessage then SendMessage (Dispatcher.cs:715-767 -> OutboundMessageQueue.cs:54-131):
+ * gd_route_device, then the send stage on the route's own device outputs (silo, status), no host round
+ * trip. */
+int gd_route_send_device(gd_handle* h, const gd_key* d_keys, uint32_t n, const uint8_t* d_category,
+                         const int64_t* d_ttl, uint32_t* d_silo, uint32_t* d_act, uint8_t* d_status,
+                         uint8_t* d_send_status, uint32_t* d_queue, uint32_t* d_perm, uint32_t* d_offsets);
+/* Host pointers, synchronous. */
+int gd_route_send(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* category, const int64_t* ttl,
+                  uint32_t* out_silo, uint32_t* out_act, uint8_t* out_status, uint8_t* out_send_status,
+                  uint32_t* out_queue, uint32_t* out_perm, uint32_t* out_offsets);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

@@ -107,6 +107,9 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->cache_local);
     free_buf(h->shard_dest);
     free_buf(h->shard_hist);
+    free_buf(h->send_tab);
+    for (DevBuf& b : h->send_scr) free_buf(b);
+    for (DevBuf& b : h->send_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

@@ -129,6 +129,12 @@ struct gd_handle {
     DevBuf fr_recv[3];                // frames: TargetActivation / Direction scratch when the caller wants neither
     DevBuf recv_scr[2];               // receive with limits but no buckets wanted: perm / offsets scratch
 
+    // sender queues (gd_sendq.h, eng_send.hip): the per-silo application bucket (gd_send_configure)
+    DevBuf send_tab;
+    uint32_t send_nsilos = 0, send_nq = 0;   // 0: not configured
+    DevBuf send_scr[2];               // (bucket, tile) counts + totals; bucket ids when the caller wants none
+    DevBuf send_buf[8];               // host-pointer entry points: inputs and outputs
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;

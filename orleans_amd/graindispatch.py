@@ -24,6 +24,9 @@ ROUTE_ADDRESSED, ROUTE_UNDECODED = 5, 6
 FRAME_HAS_TARGET, FRAME_COMPLETE, FRAME_FALLBACK, FRAME_MALFORMED, FRAME_TARGET_KEYEXT = 1, 2, 4, 8, 16
 NO_ACTIVATION = 0xFFFFFFFF
 NO_SILO = 0xFFFFFFFF
+TTL_NONE = (1 << 63) - 1
+(SEND_QUEUED, SEND_LOOPBACK, SEND_EXPIRED, SEND_NO_SILO, SEND_UNKNOWN_SILO, SEND_THROWS,
+ SEND_HELD) = range(7)
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -64,6 +67,7 @@ EXPORTED_SYMBOLS = [
     "gd_fanout_multi_device", "gd_fanout_multi", "gd_fanout_multi_fetch", "gd_dir_handoff_multi",
     "gd_fanout_multi_part_device", "gd_fanout_cascade_device",
     "gd_dir_handoff_fetch",
+    "gd_send_configure", "gd_send_queues_device", "gd_send_queues", "gd_route_send_device", "gd_route_send",
 ]
 
 
@@ -255,6 +259,11 @@ def _load() -> C.CDLL:
                                                C.POINTER(gd_frame_fields), P, P, P, P]),
         "gd_receive_frames": (C.c_int, [P, P, U64, P, U32, U32, C.POINTER(gd_recv_limits), C.POINTER(gd_frame_fields),
                                         P, P, P, P]),
+        "gd_send_configure": (C.c_int, [P, P, U32, U32]),
+        "gd_send_queues_device": (C.c_int, [P, P, P, P, P, U32, P, P, P, P]),
+        "gd_send_queues": (C.c_int, [P, P, P, P, P, U32, P, P, P, P]),
+        "gd_route_send_device": (C.c_int, [P, P, U32, P, P, P, P, P, P, P, P, P]),
+        "gd_route_send": (C.c_int, [P, P, U32, P, P, P, P, P, P, P, P, P]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -713,6 +722,64 @@ class GrainDispatch:
         self._c(lib.gd_receive_device(self.h, C.c_void_p(d_tg), C.c_void_p(d_ta), C.c_void_p(d_dir or 0), n, n_ctx,
                                       None if lim is None else C.byref(lim), C.c_void_p(d_ctx), C.c_void_p(d_status),
                                       C.c_void_p(d_perm or 0), C.c_void_p(d_offsets or 0)))
+
+    # -- sender queues (OutboundMessageQueue.SendMessage) ----------------------------------
+    def send_configure(self, silo_hash, n_queues: int):
+        """gd_send_configure: silo_hash[s] = SiloAddress.GetConsistentHashCode of silo index s."""
+        sh = np.ascontiguousarray(np.asarray(silo_hash, dtype=np.int32))
+        self._c(lib.gd_send_configure(self.h, _ptr(sh), len(sh), n_queues))
+        self.send_n_queues = n_queues
+
+    @staticmethod
+    def _opt(a, dtype):
+        return None if a is None else np.ascontiguousarray(np.asarray(a, dtype=dtype))
+
+    def send_queues(self, silo, route_status=None, category=None, ttl=None, bucket: bool = True):
+        """gd_send_queues: (send_status u8, queue u32[, perm, offsets[n_queues + 5]])."""
+        s = np.ascontiguousarray(np.asarray(silo, dtype=np.uint32))
+        n = len(s)
+        rs, cat, tl = self._opt(route_status, np.uint8), self._opt(category, np.uint8), self._opt(ttl, np.int64)
+        st = np.zeros(n, np.uint8)
+        q = np.zeros(n, np.uint32)
+        perm = np.zeros(n, np.uint32) if bucket else None
+        off = np.zeros(self.send_n_queues + 5, np.uint32) if bucket else None
+        self._c(lib.gd_send_queues(self.h, _ptr(s), None if rs is None else _ptr(rs), None if cat is None else _ptr(cat),
+                                   None if tl is None else _ptr(tl), n, _ptr(st), _ptr(q),
+                                   None if perm is None else _ptr(perm), None if off is None else _ptr(off)))
+        return (st, q, perm, off) if bucket else (st, q)
+
+    def send_queues_device(self, d_silo: int, d_route_status: Optional[int], d_category: Optional[int],
+                           d_ttl: Optional[int], n: int, d_send_status: int, d_queue: Optional[int],
+                           d_perm: Optional[int], d_offsets: Optional[int]):
+        self._c(lib.gd_send_queues_device(self.h, C.c_void_p(d_silo), C.c_void_p(d_route_status or 0),
+                                          C.c_void_p(d_category or 0), C.c_void_p(d_ttl or 0), n,
+                                          C.c_void_p(d_send_status), C.c_void_p(d_queue or 0), C.c_void_p(d_perm or 0),
+                                          C.c_void_p(d_offsets or 0)))
+
+    def route_send(self, keys, category=None, ttl=None):
+        """gd_route_send: (status, silo, act, send_status, queue, perm, offsets[n_queues + 5])."""
+        k = keys_array(keys)
+        n = len(k)
+        cat, tl = self._opt(category, np.uint8), self._opt(ttl, np.int64)
+        silo = np.zeros(n, np.uint32)
+        act = np.zeros(n, np.uint32)
+        st = np.zeros(n, np.uint8)
+        sst = np.zeros(n, np.uint8)
+        q = np.zeros(n, np.uint32)
+        perm = np.zeros(n, np.uint32)
+        off = np.zeros(self.send_n_queues + 5, np.uint32)
+        self._c(lib.gd_route_send(self.h, _ptr(k), n, None if cat is None else _ptr(cat),
+                                  None if tl is None else _ptr(tl), _ptr(silo), _ptr(act), _ptr(st), _ptr(sst), _ptr(q),
+                                  _ptr(perm), _ptr(off)))
+        return st, silo, act, sst, q, perm, off
+
+    def route_send_device(self, d_keys: int, n: int, d_category: Optional[int], d_ttl: Optional[int], d_silo: int,
+                          d_act: int, d_status: int, d_send_status: int, d_queue: Optional[int],
+                          d_perm: Optional[int], d_offsets: Optional[int]):
+        self._c(lib.gd_route_send_device(self.h, C.c_void_p(d_keys), n, C.c_void_p(d_category or 0),
+                                         C.c_void_p(d_ttl or 0), C.c_void_p(d_silo), C.c_void_p(d_act),
+                                         C.c_void_p(d_status), C.c_void_p(d_send_status), C.c_void_p(d_queue or 0),
+                                         C.c_void_p(d_perm or 0), C.c_void_p(d_offsets or 0)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
