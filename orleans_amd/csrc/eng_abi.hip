@@ -979,35 +979,15 @@ int mb_enqueue(gd_microbatch* mb, uint32_t n, bool count_done) {
         // the 8-B index when it is current (gd_microbatch_run keys its graphs by that choice)
         if (mb_use_index(h)) {
             const Cx8Args c8 = cx8_args(h);
-            switch (h->ring_mode) {
-                case GD_RING_DIRECTORY:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_DIRECTORY, true>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, c8));
-                    break;
-                case GD_RING_CONSISTENT:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_CONSISTENT, true>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, c8));
-                    break;
-                default:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_VIRTUAL_BUCKETS, true>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, c8));
-                    break;
-            }
+            GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+                return launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<decltype(mode)::value, true>, k, n,
+                              ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, c8);
+            }));
         } else {
-            switch (h->ring_mode) {
-                case GD_RING_DIRECTORY:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_DIRECTORY>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, Cx8Args{}));
-                    break;
-                case GD_RING_CONSISTENT:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_CONSISTENT>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, Cx8Args{}));
-                    break;
-                default:
-                    GD_TRY(launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<GD_RING_VIRTUAL_BUCKETS>, k, n,
-                                  ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, Cx8Args{}));
-                    break;
-            }
+            GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+                return launch(h, "k_mb_route", g, b, ring_lds(h), k_mb_route<decltype(mode)::value>, k, n,
+                              ring_args(h), table_args(h), so, act_dst, st, mb->out_u32(d, 1), mb->ts, Cx8Args{});
+            }));
         }
     } else if (n) {
         if (!zc)
@@ -1211,19 +1191,10 @@ int split_count(gd_handle* h, const uint8_t* keep, uint32_t n_keep, uint64_t* to
     const dim3 g(blocks_for(cap, BLOCK)), b(BLOCK);
     const RingArgs r = ring_args(h);
     const uint8_t* dk = (const uint8_t*)h->churn[0].p;
-    switch (h->ring_mode) {
-        case GD_RING_DIRECTORY:
-            GD_TRY(launch(h, "k_split_mark", g, b, ring_lds(h), k_split_mark<GD_RING_DIRECTORY>, (const Slot*)h->slots,
-                          cap, r, dk, n_keep, flag));
-            break;
-        case GD_RING_CONSISTENT:
-            GD_TRY(launch(h, "k_split_mark", g, b, ring_lds(h), k_split_mark<GD_RING_CONSISTENT>, (const Slot*)h->slots,
-                          cap, r, dk, n_keep, flag));
-            break;
-        default:
-            GD_TRY(launch(h, "k_split_mark", g, b, ring_lds(h), k_split_mark<GD_RING_VIRTUAL_BUCKETS>,
-                          (const Slot*)h->slots, cap, r, dk, n_keep, flag));
-    }
+    GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+        return launch(h, "k_split_mark", g, b, ring_lds(h), k_split_mark<decltype(mode)::value>, (const Slot*)h->slots,
+                      cap, r, dk, n_keep, flag);
+    }));
     HIP_TRY(h, hipMemcpyAsync(pos, flag, (size_t)cap * 4, hipMemcpyDeviceToDevice, h->stream));
     GD_TRY(scan_device<OpAdd>(h, pos, (uint32_t)cap, false, false, "split"));
     uint32_t last[2] = {0, 0};

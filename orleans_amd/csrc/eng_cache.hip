@@ -36,11 +36,9 @@ int route_cached(gd_handle* h, const gd_key* keys, uint32_t n, uint32_t* silo, u
     GD_TRY(ensure(h, h->cbuf[1], (size_t)n * 4));
     uint32_t* hit = (uint32_t*)h->cbuf[0].p;
     uint32_t* cslot = (uint32_t*)h->cbuf[1].p;
-    switch (h->ring_mode) {
-        case GD_RING_DIRECTORY: GD_TRY(route_cached_t<GD_RING_DIRECTORY>(h, keys, n, silo, act, status, hit, cslot)); break;
-        case GD_RING_CONSISTENT: GD_TRY(route_cached_t<GD_RING_CONSISTENT>(h, keys, n, silo, act, status, hit, cslot)); break;
-        default: GD_TRY(route_cached_t<GD_RING_VIRTUAL_BUCKETS>(h, keys, n, silo, act, status, hit, cslot));
-    }
+    GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+        return route_cached_t<decltype(mode)::value>(h, keys, n, silo, act, status, hit, cslot);
+    }));
     return touch ? cache_touch(h, hit, cslot, n) : GD_OK;
 }
 
@@ -61,11 +59,9 @@ int route_cached_keyext(gd_handle* h, const gd_key* keys, const ExtArgs& x, uint
     uint32_t* cslot = (uint32_t*)h->cbuf[1].p;
     if (h->cbuf[0].bytes < (size_t)n * 4 || h->cbuf[1].bytes < (size_t)n * 4)
         return set_err(h, GD_ESTATE, "KeyExt LocalLookup without the batch's route pass");
-    switch (h->ring_mode) {
-        case GD_RING_DIRECTORY: GD_TRY(route_cached_keyext_t<GD_RING_DIRECTORY>(h, keys, x, n, silo, act, st, hit, cslot)); break;
-        case GD_RING_CONSISTENT: GD_TRY(route_cached_keyext_t<GD_RING_CONSISTENT>(h, keys, x, n, silo, act, st, hit, cslot)); break;
-        default: GD_TRY(route_cached_keyext_t<GD_RING_VIRTUAL_BUCKETS>(h, keys, x, n, silo, act, st, hit, cslot));
-    }
+    GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+        return route_cached_keyext_t<decltype(mode)::value>(h, keys, x, n, silo, act, st, hit, cslot);
+    }));
     return cache_touch(h, hit, cslot, n);
 }
 

@@ -141,17 +141,10 @@ int fan_route(gd_handle* h, const uint32_t* row_off, const uint32_t* dst, const 
               uint32_t total, uint64_t tcd, uint32_t* target, uint32_t* sender, uint32_t* silo, uint32_t* act,
               uint8_t* status, const uint32_t* d_nf, bool dev_total) {
     if (!dev_total) h->routed += total;
-    switch (h->ring_mode) {
-        case GD_RING_DIRECTORY:
-            return fan_route_launch<GD_RING_DIRECTORY>(h, row_off, dst, frontier, nf, total, tcd, target, sender, silo,
+    return with_ring_mode(h->ring_mode, [&](auto mode) {
+        return fan_route_launch<decltype(mode)::value>(h, row_off, dst, frontier, nf, total, tcd, target, sender, silo,
                                                        act, status, d_nf, dev_total);
-        case GD_RING_CONSISTENT:
-            return fan_route_launch<GD_RING_CONSISTENT>(h, row_off, dst, frontier, nf, total, tcd, target, sender, silo,
-                                                        act, status, d_nf, dev_total);
-        default:
-            return fan_route_launch<GD_RING_VIRTUAL_BUCKETS>(h, row_off, dst, frontier, nf, total, tcd, target, sender,
-                                                             silo, act, status, d_nf, dev_total);
-    }
+    });
 }
 
 template <int MODE>
@@ -179,13 +172,9 @@ int route_nodes(gd_handle* h, const uint32_t* nodes, uint32_t n, uint64_t tcd, u
     cx = var == 0;
     const bool cx8 = var == 2;
     CxMeasure m(h, meas, n);
-    switch (h->ring_mode) {
-        case GD_RING_DIRECTORY:
-            return route_nodes_mode<GD_RING_DIRECTORY>(h, nodes, n, tcd, silo, act, status, cx, cx8);
-        case GD_RING_CONSISTENT:
-            return route_nodes_mode<GD_RING_CONSISTENT>(h, nodes, n, tcd, silo, act, status, cx, cx8);
-        default: return route_nodes_mode<GD_RING_VIRTUAL_BUCKETS>(h, nodes, n, tcd, silo, act, status, cx, cx8);
-    }
+    return with_ring_mode(h->ring_mode, [&](auto mode) {
+        return route_nodes_mode<decltype(mode)::value>(h, nodes, n, tcd, silo, act, status, cx, cx8);
+    });
 }
 
 // count + compact over n_act (gd_fanout.h); returns the new frontier size.

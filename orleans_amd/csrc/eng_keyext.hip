@@ -590,19 +590,10 @@ int gd_dir_remove_silos(gd_handle* h, const uint32_t* silos, uint32_t n_silos, u
         const dim3 g((uint32_t)((h->ccap + BLOCK - 1) / BLOCK)), b(BLOCK);
         const RingArgs r = ring_args(h);
         const uint8_t* loc = (const uint8_t*)h->cache_local.p;
-        switch (h->ring_mode) {
-            case GD_RING_DIRECTORY:
-                GD_TRY(launch(h, "k_cache_adjust", g, b, ring_lds(h), k_cache_adjust<GD_RING_DIRECTORY>, h->cslots,
-                              h->ccap, r, loc, h->cache_nsilos, set, h->cctr, cnt));
-                break;
-            case GD_RING_CONSISTENT:
-                GD_TRY(launch(h, "k_cache_adjust", g, b, ring_lds(h), k_cache_adjust<GD_RING_CONSISTENT>, h->cslots,
-                              h->ccap, r, loc, h->cache_nsilos, set, h->cctr, cnt));
-                break;
-            default:
-                GD_TRY(launch(h, "k_cache_adjust", g, b, ring_lds(h), k_cache_adjust<GD_RING_VIRTUAL_BUCKETS>, h->cslots,
-                              h->ccap, r, loc, h->cache_nsilos, set, h->cctr, cnt));
-        }
+        GD_TRY(with_ring_mode(h->ring_mode, [&](auto mode) {
+            return launch(h, "k_cache_adjust", g, b, ring_lds(h), k_cache_adjust<decltype(mode)::value>, h->cslots,
+                          h->ccap, r, loc, h->cache_nsilos, set, h->cctr, cnt);
+        }));
     }
     unsigned long long c[4] = {0, 0, 0, 0};
     HIP_TRY(h, hipMemcpyAsync(c, cnt, 32, hipMemcpyDeviceToHost, h->stream));

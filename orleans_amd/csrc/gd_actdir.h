@@ -20,7 +20,7 @@
 #include "gd_common.h"
 #include "gd_dirbatch.h"
 #include "gd_frames.h"
-#include "gd_kernels.h"
+#include "gd_probe.h"
 
 namespace gd {
 

@@ -24,7 +24,8 @@
 
 #include <cstdint>
 
-#include "gd_kernels.h"
+#include "gd_radix.h"
+#include "gd_rank.h"
 
 namespace gd {
 

@@ -1,4 +1,4 @@
-// gd_cx.h -- builds and maintains the compact probe indexes (gd_kernels.h CxArgs, Cx8Args).
+// gd_cx.h -- builds and maintains the compact probe indexes (gd_probe.h CxArgs, Cx8Args).
 //
 // The indexes are derived state: index slot j is a narrow projection of directory table slot j
 // (round 6), so every directory operation keeps its semantics on the authoritative 32-B-slot table
@@ -14,7 +14,7 @@
 //                 (GrainDirectoryPartition.AddSingleActivation / RemoveActivation are O(1) dictionary
 //                 operations, GrainDirectoryPartition.cs:304-363, and activations register all the
 //                 time, Catalog.cs:540-552).
-//   k_cxd_build   the direct table (gd_kernels.h CxdArgs) from a pure 8-B index: one pass over its slots.
+//   k_cxd_build   the direct table (gd_probe.h CxdArgs) from a pure 8-B index: one pass over its slots.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,7 +22,8 @@
 
 #include "gd_common.h"
 #include "gd_dirbatch.h"
-#include "gd_kernels.h"
+#include "gd_probe.h"
+#include "gd_scan.h"
 
 namespace gd {
 

@@ -56,7 +56,7 @@
 #include <cstdint>
 
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_probe.h"
 
 namespace gd {
 

@@ -19,7 +19,7 @@
 #include "gd_cache.h"
 #include "gd_common.h"
 #include "gd_dirbatch.h"
-#include "gd_kernels.h"
+#include "gd_hash.h"
 
 namespace gd {
 

@@ -18,6 +18,7 @@
 #include <map>
 #include <unordered_map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gd_common.h"
@@ -35,6 +36,9 @@
 #include "gd_dirops.h"
 #include "gd_actdir.h"
 #include "gd_bucket2.h"
+#include "gd_route.h"
+#include "gd_radix.h"
+#include "gd_mbsort.h"
 #include "graindispatch.h"
 
 using namespace gd;
@@ -243,7 +247,7 @@ struct gd_handle {
     bool cx8_pure = false;
     Cx8Args cx8_layout{};       // its layout (types, bits), fixed at the build
     DevBuf cx8_tab;
-    // the direct table standing in for a pure 8-B index over dense N1s (gd_kernels.h CxdArgs, eng_core.hip
+    // the direct table standing in for a pure 8-B index over dense N1s (gd_probe.h CxdArgs, eng_route.hip
     // cxd_prepare).  cx_snap + tab_gen is the directory's snapshot id: every path that clears cx8_pure or
     // rebuilds / re-lays the 8-B index advances one of the two.  The table is read only under the id it was
     // built at, and built only when the previous k_route launch found the index pure under the same id.
@@ -309,6 +313,16 @@ namespace gdx {
     } while (0)
 
 inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+// f(std::integral_constant<int, MODE>) for the handle's ring mode: the kernels take it as a template argument.
+template <typename F>
+auto with_ring_mode(int ring_mode, F&& f) {
+    switch (ring_mode) {
+        case GD_RING_DIRECTORY: return f(std::integral_constant<int, GD_RING_DIRECTORY>{});
+        case GD_RING_CONSISTENT: return f(std::integral_constant<int, GD_RING_CONSISTENT>{});
+        default: return f(std::integral_constant<int, GD_RING_VIRTUAL_BUCKETS>{});
+    }
+}
 
 struct Lane {
     const void* send;

@@ -21,7 +21,8 @@
 #include <cstdint>
 
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_probe.h"
+#include "gd_scan.h"
 
 namespace gd {
 
@@ -214,7 +215,7 @@ __device__ __forceinline__ uint8_t route_node(uint32_t node, uint64_t tcd, const
 }
 
 // The compact probe indexes' walks for GrainId(tcd, node) from the home's group already read
-// (gd_kernels.h cx16_walk / cx8_walk); a key the index does not hold (want 0) or a redirect entry
+// (gd_probe.h cx16_walk / cx8_walk); a key the index does not hold (want 0) or a redirect entry
 // is probed in the directory (route_node).
 template <int MODE, int RG>
 __device__ __forceinline__ uint8_t cx_walk_node(const CxArgs& cx, const TableArgs& tab, uint32_t mp, uint32_t want,
@@ -273,7 +274,7 @@ static __global__ void __launch_bounds__(BLOCK) k_route_nodes(const uint32_t* __
     if (i >= n) return;
     uint32_t silo, act;
     uint8_t st;
-    if constexpr (CX8) {                               // the 8-B index (gd_kernels.h Cx8Args)
+    if constexpr (CX8) {                               // the 8-B index (gd_probe.h Cx8Args)
         const uint32_t node = nodes[i];
         const int t8 = cx8_type(cx8, 0, node, tcd);
         const uint32_t h = uniform_hash(0, node, tcd);
@@ -354,7 +355,7 @@ static __global__ void __launch_bounds__(BLOCK) k_fan_route(const uint32_t* __re
         }
 #pragma unroll
         for (int q = 0; q < ILP; ++q) target[q] = live[q] ? dst[j[q]] : 0u;
-        if constexpr (CX8) {                                  // the 8-B index (gd_kernels.h Cx8Args)
+        if constexpr (CX8) {                                  // the 8-B index (gd_probe.h Cx8Args)
             const int t8 = cx8_type(cx8, 0, 0, tcd);          // node grains: N0 = 0, N1 = node < 2^32
             unsigned long long s8[ILP];
             uint4 q8[ILP][CX8_GROUP / 2];
@@ -387,7 +388,7 @@ static __global__ void __launch_bounds__(BLOCK) k_fan_route(const uint32_t* __re
             }
             continue;
         }
-        if constexpr (CX) {                                   // the compact probe index (gd_kernels.h)
+        if constexpr (CX) {                                   // the compact probe index (gd_probe.h)
             const uint32_t want = cx_want(cx, tcd);
             unsigned long long sc[ILP];
             uint4 qc[ILP][RG];

@@ -20,7 +20,7 @@
 #include <cstdint>
 
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_hash.h"
 
 namespace gd {
 

@@ -43,7 +43,8 @@
 
 #include "gd_bucket2.h"
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_rank.h"
+#include "gd_scan.h"
 
 namespace gd {
 

@@ -38,7 +38,8 @@
 #include <cstdint>
 
 #include "gd_bucket2.h"
-#include "gd_kernels.h"
+#include "gd_rank.h"
+#include "gd_scan.h"
 #include "gd_msd.h"
 
 namespace gd {

@@ -9,7 +9,7 @@
 // One pass, three kernels and two small scans per batch:
 //   k_sendq_classify  reads silo (4 B), route status (1), category (1) and ttl (8) once; writes the send
 //                     status (1 B) and the bucket id (4 B); per-tile bucket counts from LDS
-//   k_radix_rowscan   (gd_kernels.h) each bucket's row of tile counts, and the bucket totals
+//   k_radix_rowscan   (gd_radix.h) each bucket's row of tile counts, and the bucket totals
 //   k_sendq_offsets   the totals' exclusive scan: offsets[B + 1]
 //   k_sendq_scatter   stable rank of each tile's messages, staged in LDS in bucket order, perm written
 //                     run by run.  No second level, no intermediate records.
@@ -26,7 +26,7 @@
 #include <cstdint>
 
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_scan.h"
 #include "graindispatch.h"
 
 namespace gd {

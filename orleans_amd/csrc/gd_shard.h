@@ -18,7 +18,8 @@
 #include <cstdint>
 
 #include "gd_common.h"
-#include "gd_kernels.h"
+#include "gd_hash.h"
+#include "gd_scan.h"
 #include "gd_keyext.h"
 
 namespace gd {

@@ -1,4 +1,4 @@
-"""The direct N1-indexed table (gd_kernels.h CxdArgs, eng_core.hip cxd_prepare): while the 8-B probe index is
+"""The direct N1-indexed table (gd_probe.h CxdArgs, eng_route.hip cxd_prepare): while the 8-B probe index is
 pure -- one grain class, N0 = 0, N1 < 2^32, every live entry held -- and the N1s are dense, k_route reads
 direct[N1] instead of probing.  The table is built (k_cxd_build) only after one whole route found the
 directory unchanged, is tied to a snapshot of the directory and never read stale.

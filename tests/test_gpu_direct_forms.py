@@ -1,8 +1,8 @@
-"""The direct-table route (gd_kernels.h k_route_d, eng_core.hip cxd_prepare) in the launch forms, the
+"""The direct-table route (gd_route.h k_route_d, eng_route.hip cxd_prepare) in the launch forms, the
 n1_max writers and the entry points test_gpu_direct.py does not reach:
 
   * k_route_d<MODE, 2, false, 0>, two messages a thread, which route_mode takes once the 8-B index is over
-    ROUTE_NT_INDEX_BYTES (capacity 2^24), and route_n1_mode's k_route_d<MODE, 1, false, 4 | 8>;
+    ROUTE_NT_INDEX_BYTES (capacity 2^24), and route_n1_device's k_route_d<MODE, 1, false, 4 | 8>;
   * xcd_tile's edges: grids of 1 to 17 workgroups (nb & 7 and nb >> 3 both vary), n at k * 256 / k * 512 +- 1,
     the edge lanes in the ragged tail and in a thread's second message;
   * every writer of CxCounters::n1_max (k_cx_types on a full build, k_cx_sync for gd_dir_upsert,
@@ -14,6 +14,11 @@ n1_max writers and the entry points test_gpu_direct.py does not reach:
 As in test_gpu_direct.py every route is compared bit for bit (status, silo, act) with the oracle and with a
 second engine that probes the directory table itself (GD_OPT_PROBE 0), and every case counts the k_cxd_build
 launches: parity alone passes with the form never taken.
+
+The last four cases pin the other launch forms of the route (GD_OPT_PROBE 0 / 2 / 3 / 4) that no other test
+reaches with a pinned option: the 24-B route's two messages a thread over a 2^24-slot table, the N1 routes over
+the 16-B index, the region-mapped routes at every key width and the two k_route_bound forms; n at one
+workgroup's share and one to either side, and n = 1.
 
 Not covered: the d <= 2^30 cap of cxd_prepare (it needs a 32 GB directory), and the linear workgroup order
 (gd_handle::route_xcd off): no handle option exposes it, so every grid here runs xcd_tile with xcd = 1."""
@@ -27,7 +32,7 @@ from test_gpu_direct import CAP, TC, _builds, _check, _expect, _owner, _pair, _s
 pytestmark = pytest.mark.gpu
 
 BIG = 1 << 24                        # the smallest capacity whose 8-B index is over ROUTE_NT_INDEX_BYTES
-ROUTE_NT_INDEX_BYTES = 64 << 20      # eng_core.hip, above route_n1_mode: route_mode's M = 2 / temporal threshold
+ROUTE_NT_INDEX_BYTES = 64 << 20      # eng_route.hip, above route_form: route_mode's M = 2 / temporal threshold
 SILOS = o.bench_silos(8)
 OTHER_TCD = o.type_code_data(o.CAT_GRAIN, 0x777)
 
@@ -137,7 +142,7 @@ def _tile_edges(a, b, spec, n_list, seed):
 
 @pytest.mark.parametrize("mode", ["D", "V"])
 def test_large_index_key_form(gd, big, mode):
-    """k_route_d<MODE, 2, false, 0> (eng_core.hip route_mode: index_bytes > ROUTE_NT_INDEX_BYTES): base =
+    """k_route_d<MODE, 2, false, 0> (eng_route.hip route_mode: index_bytes > ROUTE_NT_INDEX_BYTES): base =
     xcd_tile(..) * 512 + tid, the second message at + 256; every grid size from 1 to 17 workgroups."""
     spec = _reset(big, mode)
     assert big.stats()["table_capacity"] * 8 > ROUTE_NT_INDEX_BYTES
@@ -159,7 +164,7 @@ def test_small_index_tile_edges(gd, mode):
 
 @pytest.mark.parametrize("wire", [2, 1])
 def test_large_index_n1_stream_forms(gd, big, wire):
-    """k_route_d<MODE, 1, false, 4> (u32 headers) and <.., 8> (u64): route_n1_mode's direct && !nt branches."""
+    """k_route_d<MODE, 1, false, 4> (u32 headers) and <.., 8> (u64): route_n1_device's !nt branches with the table built."""
     rng = np.random.default_rng(23)
     spec = _reset(big, "D")
     big.set_option("wire_headers", wire)
@@ -552,3 +557,177 @@ def test_microbatch_with_the_table(gd, zero_copy):
         mb.close()
     a.close()
     b.close()
+
+
+def _two_classes(spec, G):
+    """G grains of the ping class and 50 of another: the 8-B index holds two types, so it is never pure."""
+    reg = np.concatenate([o.grain_keys(TC, np.arange(G)), o.grain_keys(0x777, np.arange(50))])
+    assert (reg[G:, 2] == np.uint64(OTHER_TCD)).all()
+    return reg, (np.arange(len(reg), dtype=np.uint32) * 2 + 1), _owner(spec, reg)
+
+
+def _share_batches(rng, share, hi):
+    """n = 1 and one below, at and one past one workgroup's share of messages; keys 0..hi-1 (some unregistered)
+    with an N0 != 0 key and a key of the other class among them."""
+    out = []
+    for n in (1, share - 1, share, share + 1):
+        q = o.grain_keys(TC, rng.integers(0, hi, size=n))
+        if n > 8:
+            q[n - 2, 0] = 5
+            q[n - 1] = o.grain_keys(0x777, np.array([3]))[0]
+        out.append(q)
+    return out
+
+
+@pytest.mark.parametrize("probe", [0, 2, 3, 4])
+def test_large_index_pinned_forms(gd, big, probe):
+    """k_route_m<MODE, 2, false, 0, ...> (route_mode over a 2^24-slot table: two messages a thread, temporal
+    keys) in the directory form (GD_OPT_PROBE 0), the 16-B index in group reads (2) and slot reads (3) and the
+    8-B index with a directory fallback (4, two grain classes: not pure, so neither the PURE form nor the
+    direct table); a workgroup's share is 512 messages."""
+    rng = np.random.default_rng(30 + probe)
+    spec = _reset(big, "D")
+    big.set_option("probe", probe)
+    b = _engine(gd, "D", CAP, 0)
+    try:
+        base = _builds(big)
+        G = 6000
+        reg, acts, own = _two_classes(spec, G)
+        for e in (big, b):
+            e.register(reg, acts, own)
+        d = o.DirectoryArrays(reg, acts, own)
+        assert big.stats()["table_capacity"] * 8 > ROUTE_NT_INDEX_BYTES
+        qs = _share_batches(rng, 512, G + 600)
+        for q in qs + qs:
+            _check(big, b, q, spec, d)
+        want = _expect(qs[3], spec, d)[0]
+        assert (want == o.ST_OK).sum() > 400 and (want == o.ST_MISS).sum() > 10
+        assert _builds(big) == base
+    finally:
+        big.set_option("probe", 4)
+        b.close()
+
+
+@pytest.mark.parametrize("wire", [2, 1])
+@pytest.mark.parametrize("probe", [2, 3])
+def test_n1_stream_index16_forms(gd, probe, wire):
+    """k_route_m<MODE, 1, false, 4 | 8, true, CX_GROUP | 1>: the N1 routes (u32 and u64 headers of a world-1
+    exchange) over the 16-B index in group reads (GD_OPT_PROBE 2) and slot reads (3); a workgroup's share is
+    256 messages."""
+    rng = np.random.default_rng(40 + probe * 2 + wire)
+    spec = o.ring_spec(SILOS, "D")
+    es = [_engine(gd, "D", CAP, p, wire_headers=wire, region_probe=0) for p in (probe, 0)]
+    G = 6000
+    reg = o.grain_keys(TC, np.arange(G))
+    acts, own = np.arange(G, dtype=np.uint32) + 7, _owner(spec, reg)
+    for e in es:
+        e.register(reg, acts, own)
+        gd.GrainDispatch.comm_init_local([e])
+    d = o.DirectoryArrays(reg, acts, own)
+    try:
+        for n in (1, 255, 256, 257):
+            n1 = rng.integers(0, G + 600, size=n)
+            if wire == 1 and n > 1:
+                n1[0] = (1 << 32) + 5                            # above 2^32; its low word a live entry's
+            q = o.grain_keys(TC, n1)
+            for e in es:
+                res = e.route_multi(q, G, no_keys=True)
+                st, silo, act = _expect(q[res["recv_idx"]], spec, d)
+                np.testing.assert_array_equal(res["status"], st)
+                np.testing.assert_array_equal(res["silo"], silo)
+                np.testing.assert_array_equal(res["act"], act)
+            if n > 1:
+                assert (st == o.ST_OK).sum() > n // 2 and (st == o.ST_MISS).sum() >= 1
+    finally:
+        for e in es:
+            e.comm_destroy()
+            e.close()
+
+
+@pytest.mark.parametrize("form", ["keys", "u32", "u64"])
+def test_region_forms(gd, form):
+    """k_route_region<MODE, 0 | 4 | 8>: a world-1 exchange with GD_OPT_REGION_PROBE 1 hands the owner its chunk
+    grouped by table region, as 24-B keys (a batch of two grain classes does not compact), u32 N1s
+    (GD_OPT_WIRE_HEADERS 2) or u64 N1s (1); a workgroup's share is 256 messages of one region."""
+    wire = 1 if form == "u64" else 2
+    rng = np.random.default_rng(50 + wire + (form == "keys"))
+    spec = o.ring_spec(SILOS, "D")
+    es = [_engine(gd, "D", CAP, p, wire_headers=wire, region_probe=1) for p in (4, 0)]
+    G = 6000
+    reg = o.grain_keys(TC, np.arange(G))
+    acts, own = np.arange(G, dtype=np.uint32) + 7, _owner(spec, reg)
+    for e in es:
+        e.register(reg, acts, own)
+        gd.GrainDispatch.comm_init_local([e])
+    es[0].set_kernel_timing(True)
+    d = o.DirectoryArrays(reg, acts, own)
+    try:
+        for n in (1, 255, 256, 257, 8 * 256 + 1):
+            q = o.grain_keys(TC, rng.integers(0, G + 600, size=n))
+            if form == "keys" and n > 1:
+                q[n // 2, 2] = np.uint64(OTHER_TCD)              # a second class: 24-B headers
+            for keep in (False, True):                           # no_keys: the N1s probed as received
+                for e in es:
+                    res = e.route_multi(q, G, no_keys=not keep)
+                    assert sorted(res["recv_idx"].tolist()) == list(range(n))
+                    st, silo, act = _expect(q[res["recv_idx"]], spec, d)
+                    np.testing.assert_array_equal(res["status"], st)
+                    np.testing.assert_array_equal(res["silo"], silo)
+                    np.testing.assert_array_equal(res["act"], act)
+                    r = o.table_region_np(q[res["recv_idx"]])    # grouped by region
+                    assert (np.diff(r.astype(np.int64)) >= 0).all()
+    finally:
+        for e in es:
+            e.comm_destroy()
+            e.close()
+
+
+@pytest.mark.parametrize("large", [False, True])
+def test_route_bound_forms(gd, big, large):
+    """k_route_bound<2, true> (an index up to ROUTE_NT_INDEX_BYTES) and <2, false> (the 2^24-slot table): a
+    diagnostic, not a route -- it reads the home group of the 8-B index only.  With one grain class, N0 = 0 and
+    N1 < 2^32 a slot matching the key's low N1 word is the key's own entry, so every message it reports found
+    (status 0) carries the oracle's silo and activation, and a key the directory does not hold is never found;
+    at load 0.37 or less most entries lie in their home group.  A workgroup's share is 512 messages."""
+    import torch
+    dev = torch.device("cuda:0")
+    rng = np.random.default_rng(60 + large)
+    if large:
+        a, spec = big, _reset(big, "D")
+    else:
+        a, spec = _engine(gd, "D", CAP, 4), o.ring_spec(SILOS, "D")
+    b = _engine(gd, "D", CAP, 0)
+    try:
+        assert (a.stats()["table_capacity"] * 8 > ROUTE_NT_INDEX_BYTES) == large
+        G = 6000
+        reg = o.grain_keys(TC, np.arange(G))
+        acts, own = np.arange(G, dtype=np.uint32) + 7, _owner(spec, reg)
+        for e in (a, b):
+            e.register(reg, acts, own)
+        d = o.DirectoryArrays(reg, acts, own)
+        found = total = 0
+        for n in (1, 511, 512, 513, 4 * 512 + 1):
+            q = o.grain_keys(TC, rng.integers(0, G + 600, size=n))
+            _check(a, b, q, spec, d)
+            wst, wsilo, wact = _expect(q, spec, d)
+            dk = torch.from_numpy(q.view(np.int64)).to(dev)
+            silo = torch.full((n + 64,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+            act = torch.full((n + 64,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+            st = torch.full((n + 64,), 0x5A, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize()                             # the fills ran on torch's stream
+            a.route_bound_device(dk.data_ptr(), n, silo.data_ptr(), act.data_ptr(), st.data_ptr())
+            a.synchronize()
+            silo, act, st = silo.cpu().numpy().view(np.uint32), act.cpu().numpy().view(np.uint32), st.cpu().numpy()
+            assert (silo[n:] == 0x5A5A5A5A).all() and (act[n:] == 0x5A5A5A5A).all() and (st[n:] == 0x5A).all()
+            hit = st[:n] == 0
+            assert set(st[:n].tolist()) <= {0, 1}
+            assert (wst[hit] == o.ST_OK).all()
+            np.testing.assert_array_equal(silo[:n][hit], wsilo[hit])
+            np.testing.assert_array_equal(act[:n][hit], wact[hit])
+            found += int(hit.sum())
+            total += int((wst == o.ST_OK).sum())
+        assert found > total // 2
+    finally:
+        b.close()
+        if not large:
+            a.close()

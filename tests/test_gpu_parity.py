@@ -944,7 +944,7 @@ def test_route_bucket_host_pipelined(gd, pinned, monkeypatch):
 
 @pytest.mark.parametrize("cap", [1 << 21, 1 << 24])
 def test_route_index_size_forms_vs_oracle(gd, cap):
-    """k_route's two launch forms, picked by the probe index's size (eng_core.hip route_mode): a
+    """k_route's two launch forms, picked by the probe index's size (eng_route.hip route_mode): a
     cache-sized index (one message a thread, non-temporal key stream) and a large one (two messages a
     thread), on a ragged batch with misses, system targets and N0 != 0 keys, against the oracle."""
     silos = o.bench_silos(8)

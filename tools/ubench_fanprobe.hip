@@ -1,4 +1,4 @@
-// Micro-benchmark of the 8-B probe index's read forms (gd_kernels.h Cx8Args) at BASELINE cfg 4's and
+// Micro-benchmark of the 8-B probe index's read forms (gd_probe.h Cx8Args) at BASELINE cfg 4's and
 // cfg 2's shapes: N random probes of present keys into an index of C 8-B slots {key, value}, linear
 // probing in aligned 8-slot (64-B) groups, with a 4-B/probe key stream in and 8 B/probe out (the
 // fan-out's dst read and silo/act write).  Forms:
