@@ -945,6 +945,93 @@ int gd_route_send(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* c
                   uint32_t* out_silo, uint32_t* out_act, uint8_t* out_status, uint8_t* out_send_status,
                   uint32_t* out_queue, uint32_t* out_perm, uint32_t* out_offsets);
 
+/* ---- placement of unregistered grains (Dispatcher.AddressMessageAsync's slow path) -------------
+ * A message to a grain with no directory entry leaves the route GD_ROUTE_MISS; in the reference each such
+ * message then takes four steps (Dispatcher.cs:742-767): PlacementDirectorsManager.SelectOrAddActivation
+ * (PlacementDirectorsManager.cs:79-116) asks the grain class's placement director for a silo,
+ * AddSingleActivation registers the new address, first wins (GrainDirectoryPartition.cs:304-326),
+ * SetTargetPlacement writes it into the headers, and IsNewPlacement is set on the message that caused the
+ * activation (Dispatcher.cs:753-767).  gd_route_place* does the four for a whole batch after the route:
+ * one call leaves the batch addressed (and, in the *_bucket forms, bucketed), new grains included.
+ *
+ * Strategy, one byte a message (d_strategy) or default_strategy for all (d_strategy NULL):
+ *   GD_PLACE_NONE   no placement: the message stays GD_ROUTE_MISS, as gd_route leaves it
+ *   GD_PLACE_HASH   HashBasedPlacementDirector.cs:11-14: sorted_compatible[(uniform hash & 0x7fffffff)
+ *                   % count], the compatible silos ordered by SiloAddress.CompareTo (gd_silo_compare)
+ *   GD_PLACE_LOCAL  PreferLocalPlacementDirector.cs:17-26: gd_config.my_silo when the local silo is active
+ *                   and compatible; otherwise the reference falls back to a random silo: here to
+ *                   given_silo[i] when a given array is passed, else the message is skipped
+ *   GD_PLACE_GIVEN  given_silo[i]: RandomPlacementDirector and ActivationCountPlacementDirector.cs:89-122
+ *                   draw SafeRandom, so C# makes the choice and the library applies it (no given array:
+ *                   skipped)
+ * StatelessWorker grains (many activations, always local) are not placed here.
+ *
+ * Candidates: the messages that end the route GD_ROUTE_MISS and whose UniqueKey category is Grain (a Client
+ * target is never placed, PlacementDirectorsManager.cs:85-93,108-109).  Every other message -- KeyExt grains,
+ * system targets, the membership grain, GD_ROUTE_MULTI_ACT, hits -- keeps place status GD_PLACED_NONE and the
+ * three outputs gd_route gives, bit for bit.  A candidate is GD_PLACED_SKIPPED, and stays GD_ROUTE_MISS, when
+ * its strategy is NONE (or no known value), the compatible set is empty, LOCAL falls back without a given
+ * silo, or the chosen silo is >= n_silos, not compatible, or not valid under gd_dir_set_valid_silos (the
+ * IsValidSilo check of AddSingleActivation, GrainDirectoryPartition.cs:310).
+ *
+ * The batch equals the sequential order.  Walking the batch in order with c = 0: each non-skipped candidate
+ * proposes activation act_base + c and increments c; if its grain is still absent it registers (proposal,
+ * chosen silo) and leaves GD_ROUTE_OK with that address, GD_PLACED_NEW (the reference's IsNewPlacement); if
+ * an earlier message of the batch registered the grain it leaves GD_ROUTE_OK with the winner's address,
+ * GD_PLACED_JOINED.  Activation numbers are therefore sparse: a grain gets act_base + the rank of its first
+ * placing message among the batch's placing candidates.  *out_n_proposed = the final c: the host advances
+ * act_base by it.  A skipped message stays GD_ROUTE_MISS even when a later message of the batch places its
+ * grain: its slow path in C# then finds the entry (the strategy is a property of the grain class, so a grain's
+ * messages agree in practice).
+ *
+ * d_placed[n] receives the place status; d_new_idx (n entries, may be NULL) the ordered list of the
+ * *out_n_new messages that created an entry: exactly the list the host creates its ActivationData from.
+ * out_n_new and out_n_proposed are host words in every form: the device forms synchronise the handle's
+ * stream to deliver them (once for a batch with no candidate; around the directory batch otherwise).
+ * act_base + n_proposed reaching GD_ACT_MULTI fails with GD_EINVAL, nothing registered (the outputs are then
+ * undefined).  The *_bucket forms run the bucketing (gd_bucket) on the final act array: a newly placed message
+ * lands in its new activation's bucket, an act >= n_act in the unrouted bucket.  gd_stats.routed counts each
+ * message once.  Inside a hipGraph capture, and on a handle in cache mode (gd_cache_configure: placement is
+ * the directory owner's), the calls return GD_ESTATE without launching anything.
+ *
+ * gd_place_configure: the silo table (host pointers), compatible[s] != 0 = silo s can host the grains of the
+ * batches that follow (NULL = all), local_active != 0 = the local silo's status is Active.  1 <= n_silos <=
+ * 0xFFFE and silos non-NULL, else GD_EINVAL.  Sorts the compatible silos with gd_silo_compare; synchronises
+ * the handle first (a batch in flight reads the table it was enqueued with); may be called again after a
+ * membership change.  The batch calls return GD_ESTATE before it (a NULL handle has no configuration:
+ * GD_ESTATE too, after the argument checks). */
+#define GD_PLACE_NONE  0
+#define GD_PLACE_HASH  1
+#define GD_PLACE_LOCAL 2
+#define GD_PLACE_GIVEN 3
+#define GD_PLACED_NONE    0
+#define GD_PLACED_NEW     1
+#define GD_PLACED_JOINED  2
+#define GD_PLACED_SKIPPED 3
+int gd_place_configure(gd_handle* h, const gd_silo_addr* silos, uint32_t n_silos, const uint8_t* compatible,
+                       int local_active);
+int gd_route_place_device(gd_handle* h, const gd_key* d_keys, uint32_t n, const uint8_t* d_strategy,
+                          int default_strategy, const uint32_t* d_given_silo, uint32_t act_base, uint32_t* d_silo,
+                          uint32_t* d_act, uint8_t* d_status, uint8_t* d_placed, uint32_t* d_new_idx,
+                          uint32_t* out_n_new, uint32_t* out_n_proposed);
+/* Host pointers, synchronous. */
+int gd_route_place(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* strategy, int default_strategy,
+                   const uint32_t* given_silo, uint32_t act_base, uint32_t* out_silo, uint32_t* out_act,
+                   uint8_t* out_status, uint8_t* out_placed, uint32_t* out_new_idx, uint32_t* out_n_new,
+                   uint32_t* out_n_proposed);
+/* ... then the bucketing of the final act array: d_perm[n], d_offsets[n_act + 2] as gd_route_bucket_device. */
+int gd_route_place_bucket_device(gd_handle* h, const gd_key* d_keys, uint32_t n, const uint8_t* d_strategy,
+                                 int default_strategy, const uint32_t* d_given_silo, uint32_t act_base,
+                                 uint32_t* d_silo, uint32_t* d_act, uint8_t* d_status, uint8_t* d_placed,
+                                 uint32_t* d_new_idx, uint32_t* out_n_new, uint32_t* out_n_proposed, uint32_t n_act,
+                                 uint32_t* d_perm, uint32_t* d_offsets);
+/* Host pointers, synchronous. */
+int gd_route_place_bucket(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* strategy,
+                          int default_strategy, const uint32_t* given_silo, uint32_t act_base, uint32_t* out_silo,
+                          uint32_t* out_act, uint8_t* out_status, uint8_t* out_placed, uint32_t* out_new_idx,
+                          uint32_t* out_n_new, uint32_t* out_n_proposed, uint32_t n_act, uint32_t* out_perm,
+                          uint32_t* out_offsets);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

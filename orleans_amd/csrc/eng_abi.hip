@@ -110,6 +110,10 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->send_tab);
     for (DevBuf& b : h->send_scr) free_buf(b);
     for (DevBuf& b : h->send_buf) free_buf(b);
+    free_buf(h->place_sorted);
+    free_buf(h->place_compat);
+    for (DevBuf& b : h->place_scr) free_buf(b);
+    for (DevBuf& b : h->place_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

@@ -139,6 +139,14 @@ struct gd_handle {
     DevBuf send_scr[2];               // (bucket, tile) counts + totals; bucket ids when the caller wants none
     DevBuf send_buf[8];               // host-pointer entry points: inputs and outputs
 
+    // placement of unregistered grains (gd_place.h, eng_place.hip): the compatible silos in
+    // SiloAddress.CompareTo order and their bitset (gd_place_configure)
+    DevBuf place_sorted, place_compat;
+    uint32_t place_nsilos = 0, place_ncomp = 0;   // place_nsilos 0: not configured
+    bool place_local = false;         // the local silo is active, in the table and compatible
+    DevBuf place_scr[7];              // tile counts, block counts; candidates' idx, keys, vals, winners, inserted
+    DevBuf place_buf[4];              // host-pointer entry points: strategy, given silo, placed, new_idx
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;

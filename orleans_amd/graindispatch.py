@@ -27,6 +27,8 @@ NO_SILO = 0xFFFFFFFF
 TTL_NONE = (1 << 63) - 1
 (SEND_QUEUED, SEND_LOOPBACK, SEND_EXPIRED, SEND_NO_SILO, SEND_UNKNOWN_SILO, SEND_THROWS,
  SEND_HELD) = range(7)
+PLACE_NONE, PLACE_HASH, PLACE_LOCAL, PLACE_GIVEN = range(4)
+PLACED_NONE, PLACED_NEW, PLACED_JOINED, PLACED_SKIPPED = range(4)
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -68,6 +70,8 @@ EXPORTED_SYMBOLS = [
     "gd_fanout_multi_part_device", "gd_fanout_cascade_device",
     "gd_dir_handoff_fetch",
     "gd_send_configure", "gd_send_queues_device", "gd_send_queues", "gd_route_send_device", "gd_route_send",
+    "gd_place_configure", "gd_route_place_device", "gd_route_place", "gd_route_place_bucket_device",
+    "gd_route_place_bucket",
 ]
 
 
@@ -264,6 +268,14 @@ def _load() -> C.CDLL:
         "gd_send_queues": (C.c_int, [P, P, P, P, P, U32, P, P, P, P]),
         "gd_route_send_device": (C.c_int, [P, P, U32, P, P, P, P, P, P, P, P, P]),
         "gd_route_send": (C.c_int, [P, P, U32, P, P, P, P, P, P, P, P, P]),
+        "gd_place_configure": (C.c_int, [P, P, U32, P, C.c_int]),
+        "gd_route_place_device": (C.c_int, [P, P, U32, P, C.c_int, P, U32, P, P, P, P, P, C.POINTER(U32),
+                                            C.POINTER(U32)]),
+        "gd_route_place": (C.c_int, [P, P, U32, P, C.c_int, P, U32, P, P, P, P, P, C.POINTER(U32), C.POINTER(U32)]),
+        "gd_route_place_bucket_device": (C.c_int, [P, P, U32, P, C.c_int, P, U32, P, P, P, P, P, C.POINTER(U32),
+                                                   C.POINTER(U32), U32, P, P]),
+        "gd_route_place_bucket": (C.c_int, [P, P, U32, P, C.c_int, P, U32, P, P, P, P, P, C.POINTER(U32),
+                                            C.POINTER(U32), U32, P, P]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -780,6 +792,59 @@ class GrainDispatch:
                                          C.c_void_p(d_ttl or 0), C.c_void_p(d_silo), C.c_void_p(d_act),
                                          C.c_void_p(d_status), C.c_void_p(d_send_status), C.c_void_p(d_queue or 0),
                                          C.c_void_p(d_perm or 0), C.c_void_p(d_offsets or 0)))
+
+    # -- placement of unregistered grains (Dispatcher.AddressMessageAsync's slow path) -----------
+    def place_configure(self, silos: Sequence[Tuple[str, int, int]], compatible=None, local_active: bool = True):
+        """gd_place_configure: the silo table [(ip, port, generation)], compatible flags (None = all)."""
+        arr = (gd_silo_addr * max(1, len(silos)))(*[silo_addr(*s) for s in silos])
+        c = self._opt(compatible, np.uint8)
+        self._c(lib.gd_place_configure(self.h, arr, len(silos), None if c is None else _ptr(c), int(local_active)))
+
+    def route_place(self, keys, act_base: int, strategy=PLACE_HASH, given_silo=None):
+        """gd_route_place: (status, silo, act, placed u8, new_idx u32[n_new], n_proposed).  strategy: one
+        GD_PLACE_* value for the batch, or a u8 array with one a message."""
+        return self._route_place(keys, act_base, strategy, given_silo, None)
+
+    def route_place_bucket(self, keys, n_act: int, act_base: int, strategy=PLACE_HASH, given_silo=None):
+        """gd_route_place_bucket: (status, silo, act, placed, new_idx, n_proposed, perm, offsets[n_act + 2])."""
+        return self._route_place(keys, act_base, strategy, given_silo, n_act)
+
+    def _route_place(self, keys, act_base, strategy, given_silo, n_act):
+        k = keys_array(keys)
+        n = len(k)
+        per = None if np.isscalar(strategy) else np.ascontiguousarray(np.asarray(strategy, dtype=np.uint8))
+        dflt = int(strategy) if per is None else PLACE_NONE
+        gv = self._opt(given_silo, np.uint32)
+        silo = np.zeros(n, np.uint32)
+        act = np.zeros(n, np.uint32)
+        st = np.zeros(n, np.uint8)
+        placed = np.zeros(n, np.uint8)
+        new_idx = np.zeros(max(n, 1), np.uint32)
+        n_new, n_prop = C.c_uint32(0), C.c_uint32(0)
+        head = (self.h, _ptr(k), n, None if per is None else _ptr(per), dflt, None if gv is None else _ptr(gv),
+                act_base, _ptr(silo), _ptr(act), _ptr(st), _ptr(placed), _ptr(new_idx), C.byref(n_new), C.byref(n_prop))
+        if n_act is None:
+            self._c(lib.gd_route_place(*head))
+            return st, silo, act, placed, new_idx[:n_new.value].copy(), n_prop.value
+        perm = np.zeros(n, np.uint32)
+        off = np.zeros(n_act + 2, np.uint32)
+        self._c(lib.gd_route_place_bucket(*head, n_act, _ptr(perm), _ptr(off)))
+        return st, silo, act, placed, new_idx[:n_new.value].copy(), n_prop.value, perm, off
+
+    def route_place_device(self, d_keys: int, n: int, d_strategy: Optional[int], default_strategy: int,
+                           d_given_silo: Optional[int], act_base: int, d_silo: int, d_act: int, d_status: int,
+                           d_placed: int, d_new_idx: Optional[int], n_act: Optional[int] = None,
+                           d_perm: Optional[int] = None, d_offsets: Optional[int] = None) -> Tuple[int, int]:
+        """gd_route_place_device, or gd_route_place_bucket_device when n_act is given: (n_new, n_proposed)."""
+        n_new, n_prop = C.c_uint32(0), C.c_uint32(0)
+        head = (self.h, C.c_void_p(d_keys), n, C.c_void_p(d_strategy or 0), default_strategy,
+                C.c_void_p(d_given_silo or 0), act_base, C.c_void_p(d_silo), C.c_void_p(d_act), C.c_void_p(d_status),
+                C.c_void_p(d_placed), C.c_void_p(d_new_idx or 0), C.byref(n_new), C.byref(n_prop))
+        if n_act is None:
+            self._c(lib.gd_route_place_device(*head))
+        else:
+            self._c(lib.gd_route_place_bucket_device(*head, n_act, C.c_void_p(d_perm or 0), C.c_void_p(d_offsets or 0)))
+        return n_new.value, n_prop.value
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
