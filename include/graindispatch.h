@@ -1032,6 +1032,117 @@ int gd_route_place_bucket(gd_handle* h, const gd_key* keys, uint32_t n, const ui
                           uint32_t* out_n_new, uint32_t* out_n_proposed, uint32_t n_act, uint32_t* out_perm,
                           uint32_t* out_offsets);
 
+/* ---- turn admission of a received batch (Dispatcher.ReceiveRequest) --------------------------------
+ * What the closure IncomingMessageAgent enqueues does per message: Dispatcher.ReceiveMessage
+ * (Core/Dispatcher.cs:75-123) -> ReceiveResponse (:238-254) or ReceiveRequest (:262-301) ->
+ * ActivationMayAcceptRequest / CanInterleave (:313-336), HandleIncomingRequest (:399-424), EnqueueRequest
+ * (:431-466), ProcessRequestToInvalidActivation (:468-484).  Under lock(activation), in arrival order, every
+ * message of a received batch gets one outcome; gd_turns* gives all of them after gd_receive found the
+ * activations, so the host takes no per-message lock.
+ *
+ * The batch model is gd_receive's: the InvokeWorkItem HandleIncomingRequest queues goes on the same
+ * WorkItemGroup FIFO (WorkItemGroup.cs:174-201) as the batch's remaining closures, so no request of an
+ * activation completes (ResetRunning never runs) between two receives of one batch.
+ *
+ * Per message: ctx and recv_status as gd_receive gave them, direction as for gd_receive (1 = Response, 0xFF =
+ * absent = Request), ttl as for gd_send_queues (GD_TTL_NONE = no value), forward_count (Message.ForwardCount),
+ * a GD_MSG_* flag byte, TargetActivation and SendingActivation.  Per context: a GD_CTX_* flag byte,
+ * num_running (ActivationData.numRunning) and request_count = GetRequestCount() of the context once the agent
+ * has enqueued the whole batch, i.e. gd_recv_limits.request_count[c] plus the messages gd_receive enqueued on
+ * c (offsets[c + 1] - offsets[c]).
+ *
+ * Only messages with recv_status GD_RECV_ACTIVATION and ctx < n_ctx take part; every other message gets
+ * GD_TURN_NONE and touches no state.  For a participating message of context c, with local copies of
+ * num_running, has_running, running_ro and count (= request_count[c]), in arrival order:
+ *   1. ttl has a value and ttl <= 0: GD_TURN_EXPIRED (:79-85, Message.cs:293-302).
+ *   2. Response: GD_TURN_RESPONSE_DROPPED on an INVALID activation, else GD_TURN_RESPONSE.
+ *   3. Request / OneWay on an INVALID activation: GD_TURN_FORWARD if forward_count < max_forward_count
+ *      (MayForward, :627-630), else GD_TURN_REJECT_TRANSIENT (:563-568).
+ *   4. accepted iff the state is VALID and (num_running == 0 or can_interleave), where can_interleave =
+ *      ALWAYS_INTERLEAVE || !has_running || (running_ro && READ_ONLY) || (allow_call_chain_reentrancy &&
+ *      TargetActivation == SendingActivation) || REENTRANT || MAY_INTERLEAVE (:326-336).
+ *   5. accepted: GD_TURN_START; num_running++; if !has_running this message becomes Running and running_ro
+ *      is its READ_ONLY flag (RecordRunning, ActivationData.cs:475-493).
+ *   6. not accepted (EnqueueRequest): limit = the stateless-worker limit for a STATELESS_WORKER context, else
+ *      hard_limit; limit > 0 && count > limit: GD_TURN_REJECT_OVERLOADED ("Overload2"); else STUCK:
+ *      GD_TURN_STUCK; else GD_TURN_WAIT and count++ (the waiting list counts).
+ *   7. count-- after any outcome (the closure's finally, IncomingMessageAgent.cs:184-187).
+ * Outputs: d_turn[n]; d_num_running_out[n_ctx]; d_running_idx[n_ctx] = the batch index of the message that
+ * became Running, else 0xFFFFFFFF; d_start_idx[n] holds the *d_n_start START messages in arrival order (the
+ * InvokeWorkItems to queue; d_n_start is a device word in the *_device forms, nothing is read back);
+ * d_wait_perm[n] / d_wait_offsets[n_ctx + 2] = the stable bucketing (gd_bucket's layout) of the WAIT messages
+ * by context, every other message in the trailing bucket n_ctx: bucket c is what is appended to context c's
+ * waiting list.
+ *
+ * Optional arrays: recv_status, direction, ttl, forward_count and msg_flags may be NULL (all-activation,
+ * Request, no TTL, 0, 0).  The two activation key arrays are both given or both NULL (one alone: GD_EINVAL);
+ * in the fused form the sending array alone may be NULL.  start_idx with n_start, and wait_perm with
+ * wait_offsets, are each both or neither.  state, d_turn (n > 0), and with n_ctx > 0 ctx_flags, num_running,
+ * d_num_running_out and d_running_idx are required; request_count is required when a limit is > 0.  n == 0 is
+ * valid (the context outputs and list heads are still written).  n <= 2^31.  The calls are enqueue-only on the
+ * handle's stream but return GD_ESTATE inside a hipGraph capture, as gd_route_place does (the bucketing they
+ * reuse times its variants).
+ *
+ * Left to C#: deadlock detection (:277-293, off by default), the interface-version check of
+ * HandleIncomingRequest (:403-410), TryRescheduleCollection (:118), logging, and the cross-cluster return in
+ * TryForwardRequest.  A frame-fed form is not offered: gd_frame_fields has no read-only / interleave / TTL /
+ * forward-count outputs, and growing that struct breaks its callers (GD_ABI_VERSION stays 1). */
+#define GD_TURN_NONE              0
+#define GD_TURN_START             1
+#define GD_TURN_WAIT              2
+#define GD_TURN_REJECT_OVERLOADED 3
+#define GD_TURN_STUCK             4
+#define GD_TURN_FORWARD           5
+#define GD_TURN_REJECT_TRANSIENT  6
+#define GD_TURN_EXPIRED           7
+#define GD_TURN_RESPONSE          8
+#define GD_TURN_RESPONSE_DROPPED  9
+#define GD_MSG_READ_ONLY          1u  /* Message.IsReadOnly                                       */
+#define GD_MSG_ALWAYS_INTERLEAVE  2u  /* Message.IsAlwaysInterleave                               */
+#define GD_MSG_MAY_INTERLEAVE     4u  /* the grain class's MayInterleave predicate said yes (user
+                                         code, evaluated in C#: Catalog.cs:409-417)               */
+#define GD_CTX_VALID              0u  /* ActivationState.Valid                                    */
+#define GD_CTX_NOT_READY          1u  /* Create / Activating / Deactivating (3 reads the same)     */
+#define GD_CTX_INVALID            2u
+#define GD_CTX_STATE_MASK         3u
+#define GD_CTX_HAS_RUNNING        4u  /* Running != null when the batch starts                    */
+#define GD_CTX_RUNNING_READ_ONLY  8u  /* Running.IsReadOnly                                       */
+#define GD_CTX_REENTRANT         16u  /* GrainTypeData.IsReentrant, with a live GrainInstance     */
+#define GD_CTX_STATELESS_WORKER  32u
+#define GD_CTX_STUCK             64u  /* deactivatingTime or currentRequestActiveTime > maxRequestProcessingTime
+                                         by the host's clocks before the batch (ActivationData.cs:576-594) */
+typedef struct gd_turn_state {
+    const uint8_t*  ctx_flags;       /* [n_ctx]; device memory for the *_device entry points */
+    const uint32_t* num_running;     /* [n_ctx] */
+    const uint32_t* request_count;   /* [n_ctx] */
+    int32_t  hard_limit;             /* MaxEnqueuedRequestsHardLimit; <= 0 = none */
+    int32_t  hard_limit_stateless_worker;
+    uint32_t max_forward_count;      /* SiloMessagingOptions.MaxForwardCount */
+    int32_t  allow_call_chain_reentrancy;   /* SchedulingOptions.AllowCallChainReentrancy */
+} gd_turn_state;
+int gd_turns_device(gd_handle* h, const uint32_t* d_ctx, const uint8_t* d_recv_status, const uint8_t* d_direction,
+                    const int64_t* d_ttl, const uint8_t* d_forward_count, const uint8_t* d_msg_flags,
+                    const gd_key* d_target_activation, const gd_key* d_sending_activation, uint32_t n, uint32_t n_ctx,
+                    const gd_turn_state* state, uint8_t* d_turn, uint32_t* d_num_running_out, uint32_t* d_running_idx,
+                    uint32_t* d_start_idx, uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets);
+/* Host pointers (state's arrays too; out_n_start a host word), synchronous. */
+int gd_turns(gd_handle* h, const uint32_t* ctx, const uint8_t* recv_status, const uint8_t* direction,
+             const int64_t* ttl, const uint8_t* forward_count, const uint8_t* msg_flags,
+             const gd_key* target_activation, const gd_key* sending_activation, uint32_t n, uint32_t n_ctx,
+             const gd_turn_state* state, uint8_t* out_turn, uint32_t* out_num_running, uint32_t* out_running_idx,
+             uint32_t* out_start_idx, uint32_t* out_n_start, uint32_t* out_wait_perm, uint32_t* out_wait_offsets);
+/* IncomingMessageAgent.ReceiveMessage then Dispatcher.ReceiveMessage: gd_receive_device, then the turn stage on
+ * its own device outputs (d_ctx, d_status), no host round trip.  recv_limits / d_perm / d_offsets as
+ * gd_receive_device; the call-chain test compares d_target_activation with d_sending_activation (NULL: no
+ * message matches). */
+int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_target_activation,
+                            const uint8_t* d_direction, uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                            uint32_t* d_ctx, uint8_t* d_status, uint32_t* d_perm, uint32_t* d_offsets,
+                            const int64_t* d_ttl, const uint8_t* d_forward_count, const uint8_t* d_msg_flags,
+                            const gd_key* d_sending_activation, const gd_turn_state* state, uint8_t* d_turn,
+                            uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
+                            uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

@@ -114,6 +114,8 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->place_compat);
     for (DevBuf& b : h->place_scr) free_buf(b);
     for (DevBuf& b : h->place_buf) free_buf(b);
+    for (DevBuf& b : h->turn_scr) free_buf(b);
+    for (DevBuf& b : h->turn_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

@@ -1,0 +1,203 @@
+// eng_turns.hip -- libgraindispatch: the turn admission of a received batch: Dispatcher.ReceiveMessage
+// -> ReceiveRequest per message (gd_turns.h), alone or after the receive stage.
+// Shared handle and helpers: gd_engine.h.
+#include "gd_engine.h"
+#include "gd_turns.h"
+
+namespace {
+
+struct TurnOut {
+    uint8_t* turn;
+    uint32_t *num_running, *running_idx, *start_idx, *n_start, *wait_perm, *wait_offsets;
+};
+
+// The argument checks that need no handle state (so a caller's mistake is reported the same everywhere).
+int check_turn_args(gd_handle* h, const void* ta, const void* sa, bool fused, uint32_t n, uint32_t n_ctx,
+                    const gd_turn_state* s, const TurnOut& o) {
+    if (!h) return set_err(nullptr, GD_EINVAL, "null handle");
+    if (fused ? false : (ta != nullptr) != (sa != nullptr))
+        return set_err(h, GD_EINVAL, "target and sending activation keys go together");
+    if ((o.start_idx != nullptr) != (o.n_start != nullptr)) return set_err(h, GD_EINVAL, "start_idx and n_start go together");
+    if ((o.wait_perm != nullptr) != (o.wait_offsets != nullptr))
+        return set_err(h, GD_EINVAL, "wait_perm and wait_offsets go together");
+    if (!s) return set_err(h, GD_EINVAL, "null turn state");
+    if (n_ctx && (!s->ctx_flags || !s->num_running || !o.num_running || !o.running_idx))
+        return set_err(h, GD_EINVAL, "null context array");
+    if ((s->hard_limit > 0 || s->hard_limit_stateless_worker > 0) && n_ctx && !s->request_count)
+        return set_err(h, GD_EINVAL, "a hard limit without request_count");
+    if (n && !o.turn) return set_err(h, GD_EINVAL, "null argument");
+    if (n > (1u << 31)) return set_err(h, GD_EINVAL, "turns: n > 2^31");
+    if (n_ctx >= 0xFFFFFFFDu) return set_err(h, GD_EINVAL, "n_ctx too large");
+    return GD_OK;
+}
+
+// Refused inside a hipGraph capture (the bucketing times its variants), before anything is launched.
+int check_not_capturing(gd_handle* h, const char* call) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
+    return GD_OK;
+}
+
+// The turn stage on device arrays (state's arrays device memory).
+int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uint8_t* dir, const int64_t* ttl,
+                 const uint8_t* fwd, const uint8_t* mf, const gd_key* ta, const gd_key* sa, uint32_t n, uint32_t n_ctx,
+                 const gd_turn_state* s, const TurnOut& o) {
+    StageTime stage(h, "stage:turns");
+    const dim3 gc(blocks_for(n_ctx, BLOCK)), bc(BLOCK);
+    GD_TRY(launch(h, "k_turn_init", gc, bc, 0, k_turn_init, s->num_running, n_ctx, o.num_running, o.running_idx));
+    if (n == 0) {
+        if (o.n_start) GD_TRY(launch(h, "k_fill", dim3(1), dim3(BLOCK), 0, k_fill_u32, o.n_start, 1u, 0u));
+        if (o.wait_offsets)
+            GD_TRY(launch(h, "k_fill", dim3(blocks_for(n_ctx + 2, BLOCK)), dim3(BLOCK), 0, k_fill_u32, o.wait_offsets,
+                          n_ctx + 2, 0u));
+        return GD_OK;
+    }
+    const bool limits = s->request_count && (s->hard_limit > 0 || s->hard_limit_stateless_worker > 0);
+    const bool chain = s->allow_call_chain_reentrancy && ta && sa;
+    const TurnArgs a{s->ctx_flags, s->num_running, limits ? s->request_count : nullptr, s->hard_limit,
+                     s->hard_limit_stateless_worker, s->max_forward_count, chain ? 1u : 0u};
+    const uint32_t tiles = blocks_for(n, TN_TILE);
+    GD_TRY(ensure(h, h->turn_scr[0], ((size_t)tiles + 1) * 4));
+    uint32_t* tile_cnt = (uint32_t*)h->turn_scr[0].p;
+    uint32_t *pkey = nullptr, *rank = nullptr, *roff = nullptr, *wkey = nullptr;
+    if (limits) {
+        GD_TRY(ensure(h, h->turn_scr[1], (size_t)n * 4));
+        GD_TRY(ensure(h, h->turn_scr[2], (size_t)n * 4 + 4));
+        GD_TRY(ensure(h, h->turn_scr[3], ((size_t)n_ctx + 2) * 4));
+        GD_TRY(ensure(h, h->turn_scr[4], (size_t)n * 4));
+        pkey = (uint32_t*)h->turn_scr[1].p;
+        roff = (uint32_t*)h->turn_scr[3].p;
+        rank = (uint32_t*)h->turn_scr[4].p;
+    }
+    if (o.wait_perm) {
+        GD_TRY(ensure(h, h->turn_scr[5], (size_t)n * 4));
+        wkey = (uint32_t*)h->turn_scr[5].p;
+    }
+    GD_TRY(launch(h, "k_turn_classify", dim3(tiles), dim3(TN_NT), 0, k_turn_classify, ctx, rs, dir, ttl, fwd, mf,
+                  chain ? ta : nullptr, chain ? sa : nullptr, n, n_ctx, a, o.turn, o.running_idx, pkey));
+    // each message's place among its context's participating messages: CheckOverloaded's count (gd_turns.h)
+    if (limits) GD_TRY(bucket_device(h, pkey, n, n_ctx, (uint32_t*)h->turn_scr[2].p, roff, rank));
+    GD_TRY(launch(h, "k_turn_decide", dim3(tiles), dim3(TN_NT), 0, k_turn_decide, ctx, mf, n, n_ctx, a,
+                  (const uint32_t*)o.running_idx, (const uint32_t*)rank, (const uint32_t*)roff, o.turn, o.num_running,
+                  wkey, tile_cnt, tiles));
+    GD_TRY(launch(h, "k_turn_finish", gc, bc, 0, k_turn_finish, s->ctx_flags, n_ctx, o.running_idx));
+    if (o.start_idx) {
+        GD_TRY(scan_device<OpAdd>(h, tile_cnt, tiles + 1, false, false, "turns"));
+        const uint32_t wide = ((uintptr_t)o.turn & 15u) == 0 ? 1u : 0u;
+        GD_TRY(launch(h, "k_turn_starts", dim3(tiles), dim3(TN_NT), 0, k_turn_starts, (const uint8_t*)o.turn, n, wide,
+                      (const uint32_t*)tile_cnt, tiles, o.start_idx, n, o.n_start));
+    }
+    if (o.wait_perm) GD_TRY(bucket_device(h, wkey, n, n_ctx, o.wait_perm, o.wait_offsets));
+    return GD_OK;
+}
+
+template <typename T>
+int up(gd_handle* h, DevBuf& b, const T* src, size_t count, const T** d) {
+    *d = nullptr;
+    if (!src) return GD_OK;
+    GD_TRY(h2d(h, b, src, count));
+    *d = (const T*)b.p;
+    return GD_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int gd_turns_device(gd_handle* h, const uint32_t* d_ctx, const uint8_t* d_recv_status, const uint8_t* d_direction,
+                    const int64_t* d_ttl, const uint8_t* d_forward_count, const uint8_t* d_msg_flags,
+                    const gd_key* d_target_activation, const gd_key* d_sending_activation, uint32_t n, uint32_t n_ctx,
+                    const gd_turn_state* state, uint8_t* d_turn, uint32_t* d_num_running_out, uint32_t* d_running_idx,
+                    uint32_t* d_start_idx, uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets) {
+    const TurnOut o{d_turn, d_num_running_out, d_running_idx, d_start_idx, d_n_start, d_wait_perm, d_wait_offsets};
+    GD_TRY(check_turn_args(h, d_target_activation, d_sending_activation, false, n, n_ctx, state, o));
+    if (n && !d_ctx) return set_err(h, GD_EINVAL, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_turns_device"));
+    return turns_device(h, d_ctx, d_recv_status, d_direction, d_ttl, d_forward_count, d_msg_flags, d_target_activation,
+                        d_sending_activation, n, n_ctx, state, o);
+}
+
+int gd_turns(gd_handle* h, const uint32_t* ctx, const uint8_t* recv_status, const uint8_t* direction,
+             const int64_t* ttl, const uint8_t* forward_count, const uint8_t* msg_flags,
+             const gd_key* target_activation, const gd_key* sending_activation, uint32_t n, uint32_t n_ctx,
+             const gd_turn_state* state, uint8_t* out_turn, uint32_t* out_num_running, uint32_t* out_running_idx,
+             uint32_t* out_start_idx, uint32_t* out_n_start, uint32_t* out_wait_perm, uint32_t* out_wait_offsets) {
+    const TurnOut ho{out_turn, out_num_running, out_running_idx, out_start_idx, out_n_start, out_wait_perm,
+                     out_wait_offsets};
+    GD_TRY(check_turn_args(h, target_activation, sending_activation, false, n, n_ctx, state, ho));
+    if (n && !ctx) return set_err(h, GD_EINVAL, "null argument");
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_turns"));
+    DevBuf* B = h->turn_buf;
+    const uint32_t* dctx;
+    const uint8_t *drs, *ddir, *dfwd, *dmf;
+    const int64_t* dttl;
+    const gd_key *dta, *dsa;
+    GD_TRY(h2d(h, B[0], ctx, n));
+    dctx = (const uint32_t*)B[0].p;
+    GD_TRY(up(h, B[1], recv_status, n, &drs));
+    GD_TRY(up(h, B[2], direction, n, &ddir));
+    GD_TRY(up(h, B[3], ttl, n, &dttl));
+    GD_TRY(up(h, B[4], forward_count, n, &dfwd));
+    GD_TRY(up(h, B[5], msg_flags, n, &dmf));
+    GD_TRY(up(h, B[6], target_activation, n, &dta));
+    GD_TRY(up(h, B[7], sending_activation, n, &dsa));
+    gd_turn_state ds = *state;
+    GD_TRY(up(h, B[8], state->ctx_flags, n_ctx, &ds.ctx_flags));
+    GD_TRY(up(h, B[9], state->num_running, n_ctx, &ds.num_running));
+    GD_TRY(up(h, B[10], state->request_count, n_ctx, &ds.request_count));
+    GD_TRY(ensure(h, B[11], (size_t)n + 16));
+    GD_TRY(ensure(h, B[12], (size_t)n_ctx * 4 + 4));
+    GD_TRY(ensure(h, B[13], (size_t)n_ctx * 4 + 4));
+    TurnOut o{(uint8_t*)B[11].p, (uint32_t*)B[12].p, (uint32_t*)B[13].p, nullptr, nullptr, nullptr, nullptr};
+    if (out_start_idx) {
+        GD_TRY(ensure(h, B[14], (size_t)n * 4 + 4));
+        GD_TRY(ensure(h, B[15], 4));
+        o.start_idx = (uint32_t*)B[14].p;
+        o.n_start = (uint32_t*)B[15].p;
+    }
+    if (out_wait_perm) {
+        GD_TRY(ensure(h, B[16], (size_t)n * 4 + 4));
+        GD_TRY(ensure(h, B[17], ((size_t)n_ctx + 2) * 4));
+        o.wait_perm = (uint32_t*)B[16].p;
+        o.wait_offsets = (uint32_t*)B[17].p;
+    }
+    GD_TRY(turns_device(h, dctx, drs, ddir, dttl, dfwd, dmf, dta, dsa, n, n_ctx, &ds, o));
+    GD_TRY(d2h(h, out_turn, B[11], n));
+    GD_TRY(d2h(h, out_num_running, B[12], n_ctx));
+    GD_TRY(d2h(h, out_running_idx, B[13], n_ctx));
+    if (out_start_idx) {
+        // the whole list comes down (n entries at most); the host reads the first *out_n_start
+        GD_TRY(d2h(h, out_start_idx, B[14], n));
+        GD_TRY(d2h(h, out_n_start, B[15], 1));
+    }
+    if (out_wait_perm) {
+        GD_TRY(d2h(h, out_wait_perm, B[16], n));
+        GD_TRY(d2h(h, out_wait_offsets, B[17], (size_t)n_ctx + 2));
+    }
+    return sync_checked(h);
+}
+
+int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_target_activation,
+                            const uint8_t* d_direction, uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                            uint32_t* d_ctx, uint8_t* d_status, uint32_t* d_perm, uint32_t* d_offsets,
+                            const int64_t* d_ttl, const uint8_t* d_forward_count, const uint8_t* d_msg_flags,
+                            const gd_key* d_sending_activation, const gd_turn_state* state, uint8_t* d_turn,
+                            uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
+                            uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets) {
+    const TurnOut o{d_turn, d_num_running_out, d_running_idx, d_start_idx, d_n_start, d_wait_perm, d_wait_offsets};
+    GD_TRY(check_turn_args(h, d_target_activation, d_sending_activation, true, n, n_ctx, state, o));
+    if (n && (!d_target_grain || !d_target_activation || !d_ctx || !d_status))
+        return set_err(h, GD_EINVAL, "null argument");
+    if ((d_perm != nullptr) != (d_offsets != nullptr)) return set_err(h, GD_EINVAL, "perm and offsets go together");
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_receive_turns_device"));
+    GD_TRY(receive_device(h, d_target_grain, d_target_activation, d_direction, nullptr, n, n_ctx, recv_limits, d_ctx,
+                          d_status, d_perm, d_offsets));
+    return turns_device(h, d_ctx, d_status, d_direction, d_ttl, d_forward_count, d_msg_flags, d_target_activation,
+                        d_sending_activation, n, n_ctx, state, o);
+}
+
+}  // extern "C"

@@ -147,6 +147,10 @@ struct gd_handle {
     DevBuf place_scr[7];              // tile counts, block counts; candidates' idx, keys, vals, winners, inserted
     DevBuf place_buf[4];              // host-pointer entry points: strategy, given silo, placed, new_idx
 
+    // turn admission (gd_turns.h, eng_turns.hip)
+    DevBuf turn_scr[6];               // tile counts; rank key, perm, offsets, rank (limits); wait-list key
+    DevBuf turn_buf[18];              // host-pointer entry points: inputs, context state, outputs
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;

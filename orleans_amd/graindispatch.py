@@ -29,6 +29,11 @@ TTL_NONE = (1 << 63) - 1
  SEND_HELD) = range(7)
 PLACE_NONE, PLACE_HASH, PLACE_LOCAL, PLACE_GIVEN = range(4)
 PLACED_NONE, PLACED_NEW, PLACED_JOINED, PLACED_SKIPPED = range(4)
+(TURN_NONE, TURN_START, TURN_WAIT, TURN_REJECT_OVERLOADED, TURN_STUCK, TURN_FORWARD, TURN_REJECT_TRANSIENT,
+ TURN_EXPIRED, TURN_RESPONSE, TURN_RESPONSE_DROPPED) = range(10)
+MSG_READ_ONLY, MSG_ALWAYS_INTERLEAVE, MSG_MAY_INTERLEAVE = 1, 2, 4
+CTX_VALID, CTX_NOT_READY, CTX_INVALID, CTX_STATE_MASK = 0, 1, 2, 3
+CTX_HAS_RUNNING, CTX_RUNNING_READ_ONLY, CTX_REENTRANT, CTX_STATELESS_WORKER, CTX_STUCK = 4, 8, 16, 32, 64
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -72,6 +77,7 @@ EXPORTED_SYMBOLS = [
     "gd_send_configure", "gd_send_queues_device", "gd_send_queues", "gd_route_send_device", "gd_route_send",
     "gd_place_configure", "gd_route_place_device", "gd_route_place", "gd_route_place_bucket_device",
     "gd_route_place_bucket",
+    "gd_turns_device", "gd_turns", "gd_receive_turns_device",
 ]
 
 
@@ -153,6 +159,12 @@ ACTDIR_VALID, ACTDIR_SYSTEM_TARGET, ACTDIR_STATELESS_WORKER = 1, 2, 4
 
 class gd_recv_limits(C.Structure):
     _fields_ = [("request_count", C.c_void_p), ("hard_limit", C.c_int32), ("hard_limit_stateless_worker", C.c_int32)]
+
+
+class gd_turn_state(C.Structure):
+    _fields_ = [("ctx_flags", C.c_void_p), ("num_running", C.c_void_p), ("request_count", C.c_void_p),
+                ("hard_limit", C.c_int32), ("hard_limit_stateless_worker", C.c_int32),
+                ("max_forward_count", C.c_uint32), ("allow_call_chain_reentrancy", C.c_int32)]
 
 
 GD_COMM_ID_BYTES = 128
@@ -276,6 +288,10 @@ def _load() -> C.CDLL:
                                                    C.POINTER(U32), U32, P, P]),
         "gd_route_place_bucket": (C.c_int, [P, P, U32, P, C.c_int, P, U32, P, P, P, P, P, C.POINTER(U32),
                                             C.POINTER(U32), U32, P, P]),
+        "gd_turns_device": (C.c_int, [P] + [P] * 8 + [U32, U32, C.POINTER(gd_turn_state)] + [P] * 7),
+        "gd_turns": (C.c_int, [P] + [P] * 8 + [U32, U32, C.POINTER(gd_turn_state)] + [P] * 7),
+        "gd_receive_turns_device": (C.c_int, [P, P, P, P, U32, U32, C.POINTER(gd_recv_limits), P, P, P, P, P, P, P, P,
+                                              C.POINTER(gd_turn_state)] + [P] * 7),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -845,6 +861,73 @@ class GrainDispatch:
         else:
             self._c(lib.gd_route_place_bucket_device(*head, n_act, C.c_void_p(d_perm or 0), C.c_void_p(d_offsets or 0)))
         return n_new.value, n_prop.value
+
+    # -- turn admission of a received batch (Dispatcher.ReceiveRequest) --------------------------
+    def turns(self, ctx, n_ctx: int, ctx_flags, num_running, request_count, recv_status=None, direction=None,
+              ttl=None, forward_count=None, msg_flags=None, target_activation=None, sending_activation=None,
+              hard_limit: int = 0, hard_limit_sw: int = 0, max_forward_count: int = 2, chain: bool = False,
+              lists: bool = True):
+        """gd_turns: (turn u8, num_running_out u32[n_ctx], running_idx u32[n_ctx][, start_idx u32[n_start],
+        wait_perm u32[n], wait_offsets u32[n_ctx + 2]])."""
+        c = np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        n = len(c)
+        rs, dr, tl = self._opt(recv_status, np.uint8), self._opt(direction, np.uint8), self._opt(ttl, np.int64)
+        fw, mf = self._opt(forward_count, np.uint8), self._opt(msg_flags, np.uint8)
+        ta = None if target_activation is None else keys_array(target_activation)
+        sa = None if sending_activation is None else keys_array(sending_activation)
+        fl, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        rc = self._opt(request_count, np.uint32)
+        st = gd_turn_state(None if fl is None else _ptr(fl), None if nr is None else _ptr(nr),
+                           None if rc is None else _ptr(rc), hard_limit, hard_limit_sw, max_forward_count, int(chain))
+        turn = np.zeros(n, np.uint8)
+        nro = np.zeros(n_ctx, np.uint32)
+        run = np.zeros(n_ctx, np.uint32)
+        start = np.zeros(max(n, 1), np.uint32) if lists else None
+        n_start = np.zeros(1, np.uint32) if lists else None
+        perm = np.zeros(n, np.uint32) if lists else None
+        off = np.zeros(n_ctx + 2, np.uint32) if lists else None
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_turns(self.h, _ptr(c), p(rs), p(dr), p(tl), p(fw), p(mf), p(ta), p(sa), n, n_ctx, C.byref(st),
+                             _ptr(turn), _ptr(nro), _ptr(run), p(start), p(n_start), p(perm), p(off)))
+        if not lists:
+            return turn, nro, run
+        return turn, nro, run, start[:int(n_start[0])].copy(), perm, off
+
+    @staticmethod
+    def turn_state_device(d_ctx_flags: int, d_num_running: int, d_request_count: Optional[int] = None,
+                          hard_limit: int = 0, hard_limit_sw: int = 0, max_forward_count: int = 2,
+                          chain: bool = False) -> gd_turn_state:
+        return gd_turn_state(d_ctx_flags or None, d_num_running or None, d_request_count or None, hard_limit,
+                             hard_limit_sw, max_forward_count, int(chain))
+
+    def turns_device(self, d_ctx: int, d_recv_status: Optional[int], d_direction: Optional[int], d_ttl: Optional[int],
+                     d_forward_count: Optional[int], d_msg_flags: Optional[int], d_target_activation: Optional[int],
+                     d_sending_activation: Optional[int], n: int, n_ctx: int, state: gd_turn_state, d_turn: int,
+                     d_num_running_out: int, d_running_idx: int, d_start_idx: Optional[int] = None,
+                     d_n_start: Optional[int] = None, d_wait_perm: Optional[int] = None,
+                     d_wait_offsets: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_turns_device(self.h, V(d_ctx), V(d_recv_status), V(d_direction), V(d_ttl), V(d_forward_count),
+                                    V(d_msg_flags), V(d_target_activation), V(d_sending_activation), n, n_ctx,
+                                    C.byref(state), V(d_turn), V(d_num_running_out), V(d_running_idx), V(d_start_idx),
+                                    V(d_n_start), V(d_wait_perm), V(d_wait_offsets)))
+
+    def receive_turns_device(self, d_tg: int, d_ta: int, d_dir: Optional[int], n: int, n_ctx: int, d_ctx: int,
+                             d_status: int, d_perm: Optional[int], d_offsets: Optional[int], d_ttl: Optional[int],
+                             d_forward_count: Optional[int], d_msg_flags: Optional[int],
+                             d_sending_activation: Optional[int], state: gd_turn_state, d_turn: int,
+                             d_num_running_out: int, d_running_idx: int, d_start_idx: Optional[int] = None,
+                             d_n_start: Optional[int] = None, d_wait_perm: Optional[int] = None,
+                             d_wait_offsets: Optional[int] = None, d_recv_request_count: Optional[int] = None,
+                             recv_hard_limit: int = 0, recv_hard_limit_sw: int = 0):
+        V = lambda x: C.c_void_p(x or 0)
+        lim = gd_recv_limits(d_recv_request_count, recv_hard_limit, recv_hard_limit_sw) if d_recv_request_count else None
+        self._c(lib.gd_receive_turns_device(self.h, V(d_tg), V(d_ta), V(d_dir), n, n_ctx,
+                                            None if lim is None else C.byref(lim), V(d_ctx), V(d_status), V(d_perm),
+                                            V(d_offsets), V(d_ttl), V(d_forward_count), V(d_msg_flags),
+                                            V(d_sending_activation), C.byref(state), V(d_turn), V(d_num_running_out),
+                                            V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm),
+                                            V(d_wait_offsets)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""

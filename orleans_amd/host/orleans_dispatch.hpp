@@ -869,6 +869,35 @@ struct Message {                       // the header fields the path reads/write
     uint8_t RouteStatus = 0xFF;        // GD_ROUTE_* after AddressMessages
 };
 
+// What Dispatcher.ReceiveRequests reads of a received message (Message.cs), of the activations (ActivationData.cs,
+// one entry per scheduling context) and of the options.
+struct TurnMessage {
+    uint8_t Direction = 0;                           // Message.Directions: 0 Request, 1 Response, 2 OneWay
+    std::optional<int64_t> TimeToLiveTicks;          // Message.TimeToLive when the batch is received
+    uint8_t ForwardCount = 0;
+    bool IsReadOnly = false, IsAlwaysInterleave = false;
+    bool MayInterleave = false;                      // the grain class's MayInterleave predicate (Catalog.cs:409-417)
+    ActivationId TargetActivation;
+    std::optional<ActivationId> SendingActivation;
+};
+struct TurnContexts {
+    std::vector<uint8_t> Flags;                      // GD_CTX_*
+    std::vector<uint32_t> NumRunning;
+    std::vector<uint32_t> RequestCount;              // GetRequestCount() once the agent enqueued the batch
+};
+struct TurnOptions {
+    int32_t MaxEnqueuedRequestsHardLimit = 0, MaxEnqueuedRequestsHardLimit_StatelessWorker = 0;
+    uint32_t MaxForwardCount = 2;
+    bool AllowCallChainReentrancy = false;
+};
+struct TurnResult {
+    std::vector<uint8_t> Turn;                       // GD_TURN_* per message
+    std::vector<uint32_t> NumRunning;                // per context, after the batch
+    std::vector<uint32_t> RunningIndex;              // per context: the message that became Running, else 0xFFFFFFFF
+    std::vector<uint32_t> Start;                     // the messages to invoke now, arrival order
+    std::vector<std::vector<uint32_t>> Waiting;      // per context: appended to ActivationData.waiting
+};
+
 // Batched Dispatcher.AddressMessage (Dispatcher.cs:715-767): messages whose TargetAddress is
 // complete are skipped (:718); the rest get SetTargetPlacement (Message.cs:629-639) on a hit.
 // Returns the indices that stay on the C# slow path (MISS, system target, membership grain, and
@@ -905,6 +934,46 @@ public:
             }
         }
         return slow;
+    }
+
+    // Batched Dispatcher.ReceiveMessage -> ReceiveRequest (Dispatcher.cs:75-123, :262-301) for the messages
+    // IncomingMessageAgent.ReceiveMessages enqueued: one outcome (GD_TURN_*) per message, in arrival order, with no
+    // per-message activation lock.  context / recvStatus: ReceiveMessages' outputs (recvStatus empty = every message
+    // on an activation).  Apply the result in the reference's order: Running from RunningIndex, InvokeWorkItems from
+    // Start, Waiting appended to each activation's waiting list, then the rejections and forwards by Turn.
+    TurnResult ReceiveRequests(const std::vector<uint32_t>& context, const std::vector<uint8_t>& recvStatus,
+                               const std::vector<TurnMessage>& msgs, const TurnContexts& ctx, const TurnOptions& opt) {
+        const uint32_t n = (uint32_t)context.size(), nc = (uint32_t)ctx.Flags.size();
+        std::vector<uint8_t> dir(n), fwd(n), mf(n);
+        std::vector<int64_t> ttl(n);
+        std::vector<gd_key> ta(n), sa(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            const TurnMessage& m = msgs[i];
+            dir[i] = m.Direction;
+            fwd[i] = m.ForwardCount;
+            mf[i] = (uint8_t)((m.IsReadOnly ? GD_MSG_READ_ONLY : 0u) | (m.IsAlwaysInterleave ? GD_MSG_ALWAYS_INTERLEAVE : 0u) |
+                              (m.MayInterleave ? GD_MSG_MAY_INTERLEAVE : 0u));
+            ttl[i] = m.TimeToLiveTicks ? *m.TimeToLiveTicks : GD_TTL_NONE;
+            ta[i] = m.TargetActivation.ToNative();
+            sa[i] = m.SendingActivation ? m.SendingActivation->ToNative() : gd_key{0, 0, 0};
+        }
+        const gd_turn_state st{ctx.Flags.data(), ctx.NumRunning.data(), ctx.RequestCount.data(), opt.MaxEnqueuedRequestsHardLimit,
+                               opt.MaxEnqueuedRequestsHardLimit_StatelessWorker, opt.MaxForwardCount,
+                               opt.AllowCallChainReentrancy ? 1 : 0};
+        TurnResult r;
+        r.Turn.resize(n);
+        r.NumRunning.resize(nc);
+        r.RunningIndex.resize(nc);
+        std::vector<uint32_t> start((size_t)n + 1), perm(n), off((size_t)nc + 2);
+        uint32_t nStart = 0;
+        Check(dir_.Handle(), gd_turns(dir_.Handle(), context.data(), recvStatus.empty() ? nullptr : recvStatus.data(), dir.data(),
+                                      ttl.data(), fwd.data(), mf.data(), ta.data(), sa.data(), n, nc, &st, r.Turn.data(),
+                                      r.NumRunning.data(), r.RunningIndex.data(), start.data(), &nStart, perm.data(),
+                                      off.data()));
+        r.Start.assign(start.begin(), start.begin() + nStart);
+        r.Waiting.resize(nc);
+        for (uint32_t c = 0; c < nc; ++c) r.Waiting[c].assign(perm.begin() + off[c], perm.begin() + off[c + 1]);
+        return r;
     }
 
 private:
