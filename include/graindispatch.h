@@ -1143,6 +1143,104 @@ int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd
                             uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
                             uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets);
 
+/* ---- turn completion and message pump (Dispatcher.OnActivationCompletedRequest) ---------------------
+ * The other half of the turn cycle: InvokeWorkItem.Execute's continuation (Scheduler/InvokeWorkItem.cs:50-55,
+ * 62-63) calls Dispatcher.OnActivationCompletedRequest (Core/Dispatcher.cs:822-843) = ActivationData.
+ * ResetRunning (Catalog/ActivationData.cs:495-514), then RunMessagePump (Core/Dispatcher.cs:845-874), which
+ * takes messages off the activation's waiting list (PeekNextWaitingMessage / DequeueNextWaitingMessage,
+ * ActivationData.cs:662-672) while ActivationMayAcceptRequest (:313-336) accepts the head, and starts each
+ * (HandleIncomingRequest -> RecordRunning, ActivationData.cs:475-493).  gd_turns_complete* does this for a batch
+ * of completions under the per-activation words gd_turns* already reads and writes (num_running,
+ * GD_CTX_HAS_RUNNING, GD_CTX_RUNNING_READ_ONLY), so the host takes no lock per completed request.
+ *
+ * Per completion i, in arrival order: done_ctx[i], the activation's context as in gd_turns, and done_flags[i]
+ * (the array may be NULL = all 0): GD_DONE_IS_RUNNING -- the completed message is the activation's Running as
+ * of the batch start (message.Equals(Running)); GD_DONE_PUMP_ONLY -- no request completed, this is the bare
+ * RunMessagePump Catalog.cs:1146-1158 makes when an activation turns Valid (step 1 is skipped).
+ * Per context: ctx_flags[n_ctx] (GD_CTX_*) and num_running[n_ctx], read and written as two's-complement int32
+ * in the uint32_t array (numRunning is an int; IsCurrentlyExecuting is numRunning > 0, :697-703).
+ * The waiting lists are one CSR, gd_wait_list: context c's list is positions [offsets[c], offsets[c + 1]) in
+ * FIFO order; msg[p] is the host's handle of the message (never interpreted here); flags[p] is a GD_MSG_* byte,
+ * with GD_MSG_CALL_CHAIN = TargetActivation == SendingActivation with AllowCallChainReentrancy on when the
+ * message was queued (read by these calls only).
+ *
+ * A completion with done_ctx[i] >= n_ctx takes no part (n_started_by[i] = 0).  For each other completion of
+ * context c, in arrival order, with locals nr (int32), R in {none, X, a waiting position} (X = the batch-start
+ * Running, present iff HAS_RUNNING, ro(X) = RUNNING_READ_ONLY), the list head p (from offsets[c]), event = 0:
+ *   1. unless PUMP_ONLY (ResetRunning): nr -= 1; nr == 0: event |= GD_PUMP_BECAME_IDLE (becameIdle,
+ *      TryRescheduleCollection, RunOnInactive: C#'s).  R == X and IS_RUNNING: R = none, event |=
+ *      GD_PUMP_RUNNING_CLEARED.  R == none stays none; a message started in this batch never equals a
+ *      completion of this batch.
+ *   2. state != GD_CTX_VALID: next completion (:858).
+ *   3. while p < offsets[c + 1]: f = flags[p]; accepted iff nr <= 0 || (f & ALWAYS_INTERLEAVE) || R == none ||
+ *      (ro(R) && (f & READ_ONLY)) || (f & CALL_CHAIN) || (ctx_flags[c] & REENTRANT) || (f & MAY_INTERLEAVE);
+ *      not accepted: stop.  Accepted (DequeueNextWaitingMessage, RecordRunning): nr += 1; if R == none: R = p,
+ *      ro(R) = f & READ_ONLY, event |= GD_PUMP_RUNNING_SET; p is a start triggered by completion i; p += 1.
+ * Outputs per context (a context with no taking-part completion: its inputs copied, 0 dequeued, no event):
+ * num_running_out[c]; ctx_flags_out[c] = the input byte with HAS_RUNNING / RUNNING_READ_ONLY rewritten from R;
+ * n_dequeued[c] = p - offsets[c] (the started messages of c are exactly that prefix of its list);
+ * running_pos[c] = the waiting position that is Running at the end, else 0xFFFFFFFF; event[c].
+ * Per completion and batch: n_started_by[i]; start_pos[0 .. *n_start) = all started waiting positions in the
+ * order the sequential loop would have queued their InvokeWorkItems: by triggering completion, then FIFO
+ * (*n_start a device word in the device form).  start_pos has wait_cap entries; the caller promises
+ * offsets[n_ctx] <= wait_cap (the device form also reads no list position at or past wait_cap).
+ *
+ * One answer per batch is the sequential answer: a turn started by this batch's pump is an InvokeWorkItem
+ * handed back to the host, so it completes in a later batch; waiting lists do not grow inside the batch; and
+ * activations do not interact.  nr <= 0 with R != none is an inconsistent activation and is followed
+ * literally, as gd_turns follows HAS_RUNNING with num_running == 0.  (|num_running| + list length < 2^31.)
+ *
+ * d_n_started_by, and d_start_pos with d_n_start, are optional (the latter two both or neither: GD_EINVAL).
+ * wait, and with n_ctx > 0 wait->offsets and the context arrays, are required; wait->flags when wait_cap > 0.
+ * n_done == 0 and n_ctx == 0 are valid (context outputs are still written).  n_done <= 2^31.  Enqueue-only on
+ * the handle's stream; GD_ESTATE inside a hipGraph capture, as gd_turns_device (it reuses the bucketing).
+ *
+ * Left to C#: RunningRequestsSenders, the interface-version check of HandleIncomingRequest,
+ * TryRescheduleCollection / RunOnInactive (reported through GD_PUMP_BECAME_IDLE), logging. */
+#define GD_MSG_CALL_CHAIN         8u
+#define GD_DONE_IS_RUNNING        1u
+#define GD_DONE_PUMP_ONLY         2u
+#define GD_PUMP_BECAME_IDLE       1u
+#define GD_PUMP_RUNNING_CLEARED   2u
+#define GD_PUMP_RUNNING_SET       4u
+typedef struct gd_wait_list {
+    const uint32_t* offsets;   /* [n_ctx + 1]; device memory for the *_device entry points */
+    const uint32_t* msg;       /* [offsets[n_ctx]] */
+    const uint8_t*  flags;     /* [offsets[n_ctx]] */
+} gd_wait_list;
+int gd_turns_complete_device(gd_handle* h, const uint32_t* d_done_ctx, const uint8_t* d_done_flags, uint32_t n_done,
+                             uint32_t n_ctx, const uint8_t* d_ctx_flags, const uint32_t* d_num_running,
+                             const gd_wait_list* wait, uint32_t wait_cap, uint8_t* d_ctx_flags_out,
+                             uint32_t* d_num_running_out, uint32_t* d_n_dequeued, uint32_t* d_running_pos,
+                             uint8_t* d_event, uint32_t* d_n_started_by, uint32_t* d_start_pos, uint32_t* d_n_start);
+/* Host pointers (wait's arrays too; out_n_start a host word), synchronous.  wait_cap >= offsets[n_ctx], else
+ * GD_EINVAL. */
+int gd_turns_complete(gd_handle* h, const uint32_t* done_ctx, const uint8_t* done_flags, uint32_t n_done,
+                      uint32_t n_ctx, const uint8_t* ctx_flags, const uint32_t* num_running, const gd_wait_list* wait,
+                      uint32_t wait_cap, uint8_t* out_ctx_flags, uint32_t* out_num_running, uint32_t* out_n_dequeued,
+                      uint32_t* out_running_pos, uint8_t* out_event, uint32_t* out_n_started_by,
+                      uint32_t* out_start_pos, uint32_t* out_n_start);
+/* Keeps the CSR between steps: for every context the undequeued rest of its old list (old_list NULL or
+ * old_list->offsets NULL = no old list; d_n_dequeued NULL = nothing dequeued; a count past the list's length
+ * reads as the length), then bucket c of a gd_turns result (wait_perm[n], wait_offsets[n_ctx + 2]), both in
+ * order.  Batch message i gets msg d_msg_id[i] (NULL: id_base + i) and flags d_msg_flags[i] (NULL: 0), plus
+ * GD_MSG_CALL_CHAIN when allow_call_chain_reentrancy and its two activation keys are equal (the key arrays are
+ * both given or both NULL).  d_offsets_out[n_ctx + 1] is always written; d_msg_out / d_flags_out have cap
+ * entries and nothing is written at or past cap; *d_total = the entries needed (the caller compares it with cap
+ * later; total < 2^32).  The outputs may not alias the inputs.  Enqueue-only on the handle's stream. */
+int gd_wait_list_merge_device(gd_handle* h, const gd_wait_list* old_list, const uint32_t* d_n_dequeued, uint32_t n_ctx,
+                              const uint32_t* d_wait_perm, const uint32_t* d_wait_offsets, uint32_t n,
+                              const uint32_t* d_msg_id, uint32_t id_base, const uint8_t* d_msg_flags,
+                              const gd_key* d_target_activation, const gd_key* d_sending_activation,
+                              int allow_call_chain_reentrancy, uint32_t cap, uint32_t* d_offsets_out,
+                              uint32_t* d_msg_out, uint8_t* d_flags_out, uint32_t* d_total);
+/* Host pointers, synchronous; out_total a host word. */
+int gd_wait_list_merge(gd_handle* h, const gd_wait_list* old_list, const uint32_t* n_dequeued, uint32_t n_ctx,
+                       const uint32_t* wait_perm, const uint32_t* wait_offsets, uint32_t n, const uint32_t* msg_id,
+                       uint32_t id_base, const uint8_t* msg_flags, const gd_key* target_activation,
+                       const gd_key* sending_activation, int allow_call_chain_reentrancy, uint32_t cap,
+                       uint32_t* out_offsets, uint32_t* out_msg, uint8_t* out_flags, uint32_t* out_total);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

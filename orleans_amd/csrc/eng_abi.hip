@@ -116,6 +116,8 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->place_buf) free_buf(b);
     for (DevBuf& b : h->turn_scr) free_buf(b);
     for (DevBuf& b : h->turn_buf) free_buf(b);
+    for (DevBuf& b : h->pump_scr) free_buf(b);
+    for (DevBuf& b : h->pump_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

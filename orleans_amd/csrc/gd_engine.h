@@ -151,6 +151,10 @@ struct gd_handle {
     DevBuf turn_scr[6];               // tile counts; rank key, perm, offsets, rank (limits); wait-list key
     DevBuf turn_buf[18];              // host-pointer entry points: inputs, context state, outputs
 
+    // turn completion and message pump, wait-list merge (gd_pump.h, eng_pump.hip)
+    DevBuf pump_scr[6];               // completions' perm, offsets; start counts, first positions; work list, its count
+    DevBuf pump_buf[28];              // host-pointer entry points: completion (0-13) and merge (14-27) inputs, outputs
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;

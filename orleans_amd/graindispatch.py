@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "gd_place_configure", "gd_route_place_device", "gd_route_place", "gd_route_place_bucket_device",
     "gd_route_place_bucket",
     "gd_turns_device", "gd_turns", "gd_receive_turns_device",
+    "gd_turns_complete_device", "gd_turns_complete", "gd_wait_list_merge_device", "gd_wait_list_merge",
 ]
 
 
@@ -166,6 +167,14 @@ class gd_turn_state(C.Structure):
                 ("hard_limit", C.c_int32), ("hard_limit_stateless_worker", C.c_int32),
                 ("max_forward_count", C.c_uint32), ("allow_call_chain_reentrancy", C.c_int32)]
 
+
+class gd_wait_list(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("msg", C.c_void_p), ("flags", C.c_void_p)]
+
+
+MSG_CALL_CHAIN = 8
+DONE_IS_RUNNING, DONE_PUMP_ONLY = 1, 2
+PUMP_BECAME_IDLE, PUMP_RUNNING_CLEARED, PUMP_RUNNING_SET = 1, 2, 4
 
 GD_COMM_ID_BYTES = 128
 GD_ACT_MULTI = 0xFFFFFFFE
@@ -292,6 +301,12 @@ def _load() -> C.CDLL:
         "gd_turns": (C.c_int, [P] + [P] * 8 + [U32, U32, C.POINTER(gd_turn_state)] + [P] * 7),
         "gd_receive_turns_device": (C.c_int, [P, P, P, P, U32, U32, C.POINTER(gd_recv_limits), P, P, P, P, P, P, P, P,
                                               C.POINTER(gd_turn_state)] + [P] * 7),
+        "gd_turns_complete_device": (C.c_int, [P, P, P, U32, U32, P, P, C.POINTER(gd_wait_list), U32] + [P] * 8),
+        "gd_turns_complete": (C.c_int, [P, P, P, U32, U32, P, P, C.POINTER(gd_wait_list), U32] + [P] * 8),
+        "gd_wait_list_merge_device": (C.c_int, [P, C.POINTER(gd_wait_list), P, U32, P, P, U32, P, U32, P, P, P, C.c_int,
+                                                U32, P, P, P, P]),
+        "gd_wait_list_merge": (C.c_int, [P, C.POINTER(gd_wait_list), P, U32, P, P, U32, P, U32, P, P, P, C.c_int, U32,
+                                         P, P, P, P]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -928,6 +943,84 @@ class GrainDispatch:
                                             V(d_sending_activation), C.byref(state), V(d_turn), V(d_num_running_out),
                                             V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm),
                                             V(d_wait_offsets)))
+
+    # -- turn completion and message pump (Dispatcher.OnActivationCompletedRequest) ---------------
+    def turns_complete(self, done_ctx, n_ctx: int, ctx_flags, num_running, wait_offsets, wait_flags, done_flags=None,
+                       wait_msg=None, started_by: bool = True, starts: bool = True, wait_cap: Optional[int] = None):
+        """gd_turns_complete: (num_running_out u32[n_ctx], ctx_flags_out u8[n_ctx], n_dequeued u32[n_ctx],
+        running_pos u32[n_ctx], event u8[n_ctx][, n_started_by u32[n_done]][, start_pos u32[n_start]])."""
+        dc = np.ascontiguousarray(np.asarray(done_ctx, dtype=np.uint32))
+        n_done = len(dc)
+        df = self._opt(done_flags, np.uint8)
+        fl, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        wo, wf, wm = self._opt(wait_offsets, np.uint32), self._opt(wait_flags, np.uint8), self._opt(wait_msg, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        wl = gd_wait_list(p(wo), p(wm), p(wf))
+        total = int(wo[n_ctx]) if wo is not None and len(wo) > n_ctx else 0
+        cap = total if wait_cap is None else wait_cap
+        flo, nro = np.zeros(n_ctx, np.uint8), np.zeros(n_ctx, np.uint32)
+        ndq, rpos, ev = np.zeros(n_ctx, np.uint32), np.zeros(n_ctx, np.uint32), np.zeros(n_ctx, np.uint8)
+        nsb = np.zeros(n_done, np.uint32) if started_by else None
+        start = np.zeros(max(cap, 1), np.uint32) if starts else None
+        n_start = np.zeros(1, np.uint32) if starts else None
+        self._c(lib.gd_turns_complete(self.h, _ptr(dc), p(df), n_done, n_ctx, p(fl), p(nr), C.byref(wl), cap, _ptr(flo),
+                                      _ptr(nro), _ptr(ndq), _ptr(rpos), _ptr(ev), p(nsb), p(start), p(n_start)))
+        out = (nro, flo, ndq, rpos, ev)
+        if started_by:
+            out += (nsb,)
+        if starts:
+            out += (start[:int(n_start[0])].copy(),)
+        return out
+
+    @staticmethod
+    def wait_list_device(d_offsets: Optional[int], d_msg: Optional[int], d_flags: Optional[int]) -> gd_wait_list:
+        return gd_wait_list(d_offsets or None, d_msg or None, d_flags or None)
+
+    def turns_complete_device(self, d_done_ctx: Optional[int], d_done_flags: Optional[int], n_done: int, n_ctx: int,
+                              d_ctx_flags: int, d_num_running: int, wait: gd_wait_list, wait_cap: int,
+                              d_ctx_flags_out: int, d_num_running_out: int, d_n_dequeued: int, d_running_pos: int,
+                              d_event: int, d_n_started_by: Optional[int] = None, d_start_pos: Optional[int] = None,
+                              d_n_start: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_turns_complete_device(self.h, V(d_done_ctx), V(d_done_flags), n_done, n_ctx, V(d_ctx_flags),
+                                             V(d_num_running), C.byref(wait), wait_cap, V(d_ctx_flags_out),
+                                             V(d_num_running_out), V(d_n_dequeued), V(d_running_pos), V(d_event),
+                                             V(d_n_started_by), V(d_start_pos), V(d_n_start)))
+
+    def wait_list_merge(self, n_ctx: int, old_offsets, old_msg, old_flags, n_dequeued, wait_perm, wait_offsets,
+                        msg_id=None, id_base: int = 0, msg_flags=None, target_activation=None, sending_activation=None,
+                        chain: bool = False, cap: Optional[int] = None):
+        """gd_wait_list_merge: (offsets u32[n_ctx + 1], msg u32[cap], flags u8[cap], total); the first
+        min(total, cap) entries of msg / flags are written.  old_offsets None = no old list; cap None = enough."""
+        oo, om, of = self._opt(old_offsets, np.uint32), self._opt(old_msg, np.uint32), self._opt(old_flags, np.uint8)
+        nd = self._opt(n_dequeued, np.uint32)
+        wp, wo = self._opt(wait_perm, np.uint32), self._opt(wait_offsets, np.uint32)
+        n = len(wp)
+        mi, mf = self._opt(msg_id, np.uint32), self._opt(msg_flags, np.uint8)
+        ta = None if target_activation is None else keys_array(target_activation)
+        sa = None if sending_activation is None else keys_array(sending_activation)
+        p = lambda a: None if a is None else _ptr(a)
+        if cap is None:
+            cap = (int(oo[n_ctx]) if oo is not None else 0) + n
+        old = None if oo is None else gd_wait_list(p(oo), p(om), p(of))
+        off = np.zeros(n_ctx + 1, np.uint32)
+        msg, flags = np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint8)
+        total = np.zeros(1, np.uint32)
+        self._c(lib.gd_wait_list_merge(self.h, None if old is None else C.byref(old), p(nd), n_ctx, p(wp), p(wo), n,
+                                       p(mi), id_base, p(mf), p(ta), p(sa), int(chain), cap, _ptr(off), _ptr(msg),
+                                       _ptr(flags), _ptr(total)))
+        return off, msg[:cap], flags[:cap], int(total[0])
+
+    def wait_list_merge_device(self, old: Optional[gd_wait_list], d_n_dequeued: Optional[int], n_ctx: int,
+                               d_wait_perm: Optional[int], d_wait_offsets: int, n: int, d_msg_id: Optional[int],
+                               id_base: int, d_msg_flags: Optional[int], d_target_activation: Optional[int],
+                               d_sending_activation: Optional[int], chain: bool, cap: int, d_offsets_out: int,
+                               d_msg_out: Optional[int], d_flags_out: Optional[int], d_total: int):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_wait_list_merge_device(self.h, None if old is None else C.byref(old), V(d_n_dequeued), n_ctx,
+                                              V(d_wait_perm), V(d_wait_offsets), n, V(d_msg_id), id_base, V(d_msg_flags),
+                                              V(d_target_activation), V(d_sending_activation), int(chain), cap,
+                                              V(d_offsets_out), V(d_msg_out), V(d_flags_out), V(d_total)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
