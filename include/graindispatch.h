@@ -1241,6 +1241,118 @@ int gd_wait_list_merge(gd_handle* h, const gd_wait_list* old_list, const uint32_
                        const gd_key* sending_activation, int allow_call_chain_reentrancy, uint32_t cap,
                        uint32_t* out_offsets, uint32_t* out_msg, uint8_t* out_flags, uint32_t* out_total);
 
+/* ---- callback table (InsideRuntimeClient.callbacks: SendRequest's TryAdd to ReceiveResponse) ---------
+ * The outstanding requests of a silo: InsideRuntimeClient.callbacks, ConcurrentDictionary<CorrelationId,
+ * CallbackData> (Core/InsideRuntimeClient.cs), as one table per handle in device memory, keyed by the 64-bit
+ * CorrelationId.  An entry holds the host's callback handle (u32, never interpreted here), the message's
+ * ResendCount, its TargetSilo as a silo index (GD_CB_NO_SILO = not addressed) and the deadline of its response
+ * timer (int64 ticks).  With it a send -> receive -> turn -> complete -> respond cycle takes no per-message
+ * dictionary operation on the host.  Calls are serialised by the caller, like every table of the handle; a batch
+ * gives the results of its messages taken one by one in array order.
+ *
+ * gd_callbacks_configure(capacity_hint, max_resend_count, resend_on_timeout, period_ticks): the first call
+ * creates the table (a power of two >= max(capacity_hint, 64) slots); a later call changes the options
+ * (MessagingOptions.MaxResendCount <= 255, ResendOnTimeout) and grows the table if the hint asks for more.
+ * period_ticks = timeout / (MaxResendCount + 1) when ResendOnTimeout && MaxResendCount > 0, else unused
+ * (CallbackData.StartTimer, Orleans.Core/Runtime/CallbackData.cs:80-85).  The other calls return GD_ESTATE
+ * before it.  gd_callbacks_clear empties the table; gd_callbacks_count reads the live entries and the slots.
+ * The table holds live entries and the tombstones of removed ones; when both pass 0.75 of the slots an add
+ * rebuilds it on the stream, at the same capacity while the live entries fill at most half of it, else at double;
+ * GD_EFULL only when that allocation fails.
+ *
+ * add = SendRequestMessage's callbacks.TryAdd(message.Id, callbackData) + StartTimer (:205-218), before the
+ *   message is addressed: per i, if ids[i] is absent the entry {handles[i], deadlines[i], resend 0, no target} is
+ *   added and out_added[i] = 1, else nothing changes and out_added[i] = 0 (in the table or earlier in the batch:
+ *   the first add wins).  out_added may be NULL.
+ * set_target = Message.TargetSilo once gd_route* has addressed the batch, kept for break_silo: per i, a present
+ *   ids[i] gets target silo[i] (GD_CB_NO_SILO allowed: ResendMessageImpl clears it, Core/Dispatcher.cs:618-620;
+ *   else < 0xFFFF) and out_found[i] = 1, an absent one out_found[i] = 0; the last of an id in the batch stands.
+ * lookup: read-only; out_handle (0xFFFFFFFF absent), out_resend (0), out_silo (GD_CB_NO_SILO), out_found; each
+ *   output may be NULL.
+ * respond = Dispatcher.ReceiveResponse (Core/Dispatcher.cs:238-254) -> InsideRuntimeClient.ReceiveResponse
+ *   (:569-627) -> CallbackData.DoCallback (CallbackData.cs:126-157).  Per message: id; result (0 Success, 1 Error,
+ *   2 Rejection, Message.cs:89-94; NULL array = all Success); rejection_type (0 Transient, 1 Overloaded,
+ *   2 DuplicateRequest, 3 Unrecoverable, 4 GatewayTooBusy, :96-103; read only for a rejection, NULL = Transient);
+ *   flags (NULL = 0): GD_RESP_TARGET_NOT_ME = !TargetSilo.Matches(CurrentSilo), GD_RESP_HAS_CACHE_HEADER =
+ *   CacheInvalidationHeader != null; turn (optional, the gd_turns* output byte): only messages with
+ *   turn == GD_TURN_RESPONSE take part, the others get GD_CB_NONE, flags 0, handle 0xFFFFFFFF.
+ *   Per participating message, in array order:
+ *     1. Rejection and TARGET_NOT_ME: GD_CB_GATEWAY_BACK (Transport.SendMessage is the caller's), nothing else
+ *        (:573-579).
+ *     2. Rejection of type Transient or Unrecoverable without the cache header: out_flags |=
+ *        GD_CB_INVALIDATE_CACHE (:590-600); the caller invalidates SendingAddress (gd_cache_remove).
+ *     3. id not in the table: GD_CB_NO_CALLBACK (:610,622-626).
+ *     4. found, Rejection and Transient, and resend_count < max_resend_count (Message.MayResend, Message.cs:346-349;
+ *        Dispatcher.TryResendMessage, Core/Dispatcher.cs:581-589): resend_count += 1, the target becomes none,
+ *        GD_CB_RESEND, out_handle = the entry's handle; the entry stays (CallbackData.cs:135-141).
+ *     5. otherwise GD_CB_FIRE, out_handle = the entry's handle, the entry is removed (alreadyFired, unregister:
+ *        CallbackData.cs:143-149, InsideRuntimeClient.cs:247-251).
+ *   out_handle is 0xFFFFFFFF unless RESEND or FIRE.  fire_idx / n_fire (optional, both or neither): the FIRE
+ *   messages in array order, the order callback(response, context) runs in; fire_idx has n entries.
+ *   Closed form (ids do not interact): among an id's responses that reach rule 3 and find the entry at the batch
+ *   start, with k = max(max_resend_count - resend_count, 0) and f = min(rank of the first that is not a transient
+ *   rejection, k): rank < f RESEND, rank == f FIRE, rank > f NO_CALLBACK.
+ * expire = the response timers: CallbackData.OnTimeout -> OnFail(isOnTimeout) (CallbackData.cs:97-109,179-212).
+ *   Every entry with deadline <= now, one tick an entry a call: if resend_on_timeout && resend_count <
+ *   max_resend_count: resend_count += 1, deadline += period_ticks, target none, kind GD_CB_RESEND; else it is
+ *   removed, kind GD_CB_TIMEOUT.  out_id / out_handle / out_kind [0 .. *n_out), in no particular order (timers
+ *   have none).  *n_out > cap: nothing was changed or listed (host form: GD_EINVAL; device form: the caller
+ *   compares the device word with cap).
+ * break_silo = BreakOutstandingMessagesToDeadSilo (InsideRuntimeClient.cs:726-735) -> OnTargetSiloFail
+ *   (CallbackData.cs:111-124): the same for every entry whose target is `silo`, the deadline untouched, kind
+ *   GD_CB_RESEND or GD_CB_SILO_FAILED.
+ *
+ * The *_device forms take device pointers (n_fire / n_out device words) and only enqueue on the handle's stream,
+ * except that an add whose room cannot be told from the host's bound reads the counters back (GD_ESTATE inside a
+ * hipGraph capture); they run a fixed number of gated passes: an add of new ids that did not settle in 12 claim
+ * passes, or a respond with more than 6 transient rejections resent for one id in one batch, is reported as
+ * GD_ETIMEOUT by the next synchronising gd_callbacks_* call.  The host forms are synchronous and return
+ * GD_ESTATE inside a capture.  n <= 2^31; n == 0 is valid.
+ *
+ * Left to C#: TransactionInfo.Join, the statistics, the callback invocation itself, the actual resend
+ * (ResendMessageImpl), TryDeliverToProxy, logging. */
+#define GD_CB_NONE            0
+#define GD_CB_FIRE            1
+#define GD_CB_RESEND          2
+#define GD_CB_NO_CALLBACK     3
+#define GD_CB_GATEWAY_BACK    4
+#define GD_CB_TIMEOUT         5
+#define GD_CB_SILO_FAILED     6
+#define GD_CB_INVALIDATE_CACHE  1u           /* out_flags bit */
+#define GD_RESP_TARGET_NOT_ME     1u
+#define GD_RESP_HAS_CACHE_HEADER  2u
+#define GD_CB_NO_SILO         0xFFFFFFFFu
+int gd_callbacks_configure(gd_handle* h, uint64_t capacity_hint, uint32_t max_resend_count, int resend_on_timeout,
+                           int64_t period_ticks);
+int gd_callbacks_clear(gd_handle* h);
+int gd_callbacks_count(gd_handle* h, uint64_t* out_live, uint64_t* out_capacity);
+int gd_callbacks_add_device(gd_handle* h, const int64_t* d_ids, const uint32_t* d_handles, const int64_t* d_deadlines,
+                            uint32_t n, uint8_t* d_out_added);
+int gd_callbacks_add(gd_handle* h, const int64_t* ids, const uint32_t* handles, const int64_t* deadlines, uint32_t n,
+                     uint8_t* out_added);
+int gd_callbacks_set_target_device(gd_handle* h, const int64_t* d_ids, const uint32_t* d_silo, uint32_t n,
+                                   uint8_t* d_out_found);
+int gd_callbacks_set_target(gd_handle* h, const int64_t* ids, const uint32_t* silo, uint32_t n, uint8_t* out_found);
+int gd_callbacks_lookup_device(gd_handle* h, const int64_t* d_ids, uint32_t n, uint32_t* d_out_handle,
+                               uint32_t* d_out_resend, uint32_t* d_out_silo, uint8_t* d_out_found);
+int gd_callbacks_lookup(gd_handle* h, const int64_t* ids, uint32_t n, uint32_t* out_handle, uint32_t* out_resend,
+                        uint32_t* out_silo, uint8_t* out_found);
+int gd_callbacks_respond_device(gd_handle* h, const int64_t* d_ids, const uint8_t* d_result,
+                                const uint8_t* d_rejection_type, const uint8_t* d_flags, const uint8_t* d_turn,
+                                uint32_t n, uint8_t* d_out_outcome, uint8_t* d_out_flags, uint32_t* d_out_handle,
+                                uint32_t* d_fire_idx, uint32_t* d_n_fire);
+int gd_callbacks_respond(gd_handle* h, const int64_t* ids, const uint8_t* result, const uint8_t* rejection_type,
+                         const uint8_t* flags, const uint8_t* turn, uint32_t n, uint8_t* out_outcome,
+                         uint8_t* out_flags, uint32_t* out_handle, uint32_t* fire_idx, uint32_t* n_fire);
+int gd_callbacks_expire_device(gd_handle* h, int64_t now, uint32_t cap, int64_t* d_out_id, uint32_t* d_out_handle,
+                               uint8_t* d_out_kind, uint32_t* d_n_out);
+int gd_callbacks_expire(gd_handle* h, int64_t now, uint32_t cap, int64_t* out_id, uint32_t* out_handle,
+                        uint8_t* out_kind, uint32_t* n_out);
+int gd_callbacks_break_silo_device(gd_handle* h, uint32_t silo, uint32_t cap, int64_t* d_out_id, uint32_t* d_out_handle,
+                                   uint8_t* d_out_kind, uint32_t* d_n_out);
+int gd_callbacks_break_silo(gd_handle* h, uint32_t silo, uint32_t cap, int64_t* out_id, uint32_t* out_handle,
+                            uint8_t* out_kind, uint32_t* n_out);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

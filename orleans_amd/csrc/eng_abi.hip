@@ -118,6 +118,9 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->turn_buf) free_buf(b);
     for (DevBuf& b : h->pump_scr) free_buf(b);
     for (DevBuf& b : h->pump_buf) free_buf(b);
+    for (DevBuf* b : {&h->cb_tab, &h->cb_dl, &h->cb_ctr, &h->cb_last}) free_buf(*b);
+    for (DevBuf& b : h->cb_scr) free_buf(b);
+    for (DevBuf& b : h->cb_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

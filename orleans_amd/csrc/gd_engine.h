@@ -155,6 +155,17 @@ struct gd_handle {
     DevBuf pump_scr[6];               // completions' perm, offsets; start counts, first positions; work list, its count
     DevBuf pump_buf[28];              // host-pointer entry points: completion (0-13) and merge (14-27) inputs, outputs
 
+    // callback table (gd_callbacks.h, eng_callbacks.hip): CorrelationId -> callback handle, resend count, target silo
+    DevBuf cb_tab, cb_dl, cb_ctr;     // the 16-B slots, their deadlines, CbCounters
+    DevBuf cb_last;                   // two election words a slot (zero between calls)
+    unsigned long long cb_cap = 0;    // slots; 0: not configured (gd_callbacks_configure)
+    uint64_t cb_used_ub = 0;          // live + tombstones at most: the last read-back plus every add since
+    uint32_t cb_max_resend = 0;       // MessagingOptions.MaxResendCount, ResendOnTimeout, the timer's repeat period
+    bool cb_resend_on_timeout = false;
+    int64_t cb_period = 0;
+    DevBuf cb_scr[4];                 // slot_of, is_new / class, fire tile counts, scan flags
+    DevBuf cb_buf[16];                // host-pointer entry points: inputs and outputs
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;

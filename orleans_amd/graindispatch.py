@@ -34,6 +34,10 @@ PLACED_NONE, PLACED_NEW, PLACED_JOINED, PLACED_SKIPPED = range(4)
 MSG_READ_ONLY, MSG_ALWAYS_INTERLEAVE, MSG_MAY_INTERLEAVE = 1, 2, 4
 CTX_VALID, CTX_NOT_READY, CTX_INVALID, CTX_STATE_MASK = 0, 1, 2, 3
 CTX_HAS_RUNNING, CTX_RUNNING_READ_ONLY, CTX_REENTRANT, CTX_STATELESS_WORKER, CTX_STUCK = 4, 8, 16, 32, 64
+CB_NONE, CB_FIRE, CB_RESEND, CB_NO_CALLBACK, CB_GATEWAY_BACK, CB_TIMEOUT, CB_SILO_FAILED = range(7)
+CB_INVALIDATE_CACHE = 1
+RESP_TARGET_NOT_ME, RESP_HAS_CACHE_HEADER = 1, 2
+CB_NO_SILO = 0xFFFFFFFF
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -79,6 +83,10 @@ EXPORTED_SYMBOLS = [
     "gd_route_place_bucket",
     "gd_turns_device", "gd_turns", "gd_receive_turns_device",
     "gd_turns_complete_device", "gd_turns_complete", "gd_wait_list_merge_device", "gd_wait_list_merge",
+    "gd_callbacks_configure", "gd_callbacks_clear", "gd_callbacks_count", "gd_callbacks_add_device",
+    "gd_callbacks_add", "gd_callbacks_set_target_device", "gd_callbacks_set_target", "gd_callbacks_lookup_device",
+    "gd_callbacks_lookup", "gd_callbacks_respond_device", "gd_callbacks_respond", "gd_callbacks_expire_device",
+    "gd_callbacks_expire", "gd_callbacks_break_silo_device", "gd_callbacks_break_silo",
 ]
 
 
@@ -307,6 +315,21 @@ def _load() -> C.CDLL:
                                                 U32, P, P, P, P]),
         "gd_wait_list_merge": (C.c_int, [P, C.POINTER(gd_wait_list), P, U32, P, P, U32, P, U32, P, P, P, C.c_int, U32,
                                          P, P, P, P]),
+        "gd_callbacks_configure": (C.c_int, [P, U64, U32, C.c_int, C.c_int64]),
+        "gd_callbacks_clear": (C.c_int, [P]),
+        "gd_callbacks_count": (C.c_int, [P, C.POINTER(U64), C.POINTER(U64)]),
+        "gd_callbacks_add_device": (C.c_int, [P, P, P, P, U32, P]),
+        "gd_callbacks_add": (C.c_int, [P, P, P, P, U32, P]),
+        "gd_callbacks_set_target_device": (C.c_int, [P, P, P, U32, P]),
+        "gd_callbacks_set_target": (C.c_int, [P, P, P, U32, P]),
+        "gd_callbacks_lookup_device": (C.c_int, [P, P, U32, P, P, P, P]),
+        "gd_callbacks_lookup": (C.c_int, [P, P, U32, P, P, P, P]),
+        "gd_callbacks_respond_device": (C.c_int, [P, P, P, P, P, P, U32, P, P, P, P, P]),
+        "gd_callbacks_respond": (C.c_int, [P, P, P, P, P, P, U32, P, P, P, P, P]),
+        "gd_callbacks_expire_device": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
+        "gd_callbacks_expire": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
+        "gd_callbacks_break_silo_device": (C.c_int, [P, U32, U32, P, P, P, P]),
+        "gd_callbacks_break_silo": (C.c_int, [P, U32, U32, P, P, P, P]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -1021,6 +1044,106 @@ class GrainDispatch:
                                               V(d_wait_perm), V(d_wait_offsets), n, V(d_msg_id), id_base, V(d_msg_flags),
                                               V(d_target_activation), V(d_sending_activation), int(chain), cap,
                                               V(d_offsets_out), V(d_msg_out), V(d_flags_out), V(d_total)))
+
+    # -- callback table (InsideRuntimeClient.callbacks) --------------------------------------------
+    def callbacks_configure(self, capacity_hint: int, max_resend_count: int = 0, resend_on_timeout: bool = False,
+                            period_ticks: int = 0):
+        self._c(lib.gd_callbacks_configure(self.h, capacity_hint, max_resend_count, int(resend_on_timeout),
+                                           period_ticks))
+
+    def callbacks_clear(self):
+        self._c(lib.gd_callbacks_clear(self.h))
+
+    def callbacks_count(self) -> Tuple[int, int]:
+        """gd_callbacks_count: (live entries, slots)."""
+        live, cap = C.c_uint64(0), C.c_uint64(0)
+        self._c(lib.gd_callbacks_count(self.h, C.byref(live), C.byref(cap)))
+        return int(live.value), int(cap.value)
+
+    def callbacks_add(self, ids, handles, deadlines) -> np.ndarray:
+        """gd_callbacks_add: added u8[n]."""
+        i, hd, dl = self._opt(ids, np.int64), self._opt(handles, np.uint32), self._opt(deadlines, np.int64)
+        out = np.zeros(len(i), np.uint8)
+        self._c(lib.gd_callbacks_add(self.h, _ptr(i), _ptr(hd), _ptr(dl), len(i), _ptr(out)))
+        return out
+
+    def callbacks_set_target(self, ids, silo) -> np.ndarray:
+        """gd_callbacks_set_target: found u8[n]."""
+        i, s = self._opt(ids, np.int64), self._opt(silo, np.uint32)
+        out = np.zeros(len(i), np.uint8)
+        self._c(lib.gd_callbacks_set_target(self.h, _ptr(i), _ptr(s), len(i), _ptr(out)))
+        return out
+
+    def callbacks_lookup(self, ids):
+        """gd_callbacks_lookup: (handle u32, resend u32, silo u32, found u8)."""
+        i = self._opt(ids, np.int64)
+        n = len(i)
+        hd, rs, sl, fd = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        self._c(lib.gd_callbacks_lookup(self.h, _ptr(i), n, _ptr(hd), _ptr(rs), _ptr(sl), _ptr(fd)))
+        return hd, rs, sl, fd
+
+    def callbacks_respond(self, ids, result=None, rejection_type=None, flags=None, turn=None, fire: bool = True):
+        """gd_callbacks_respond: (outcome u8, out_flags u8, handle u32[, fire_idx u32[n_fire]])."""
+        i = self._opt(ids, np.int64)
+        n = len(i)
+        rs, rj = self._opt(result, np.uint8), self._opt(rejection_type, np.uint8)
+        fl, tn = self._opt(flags, np.uint8), self._opt(turn, np.uint8)
+        p = lambda a: None if a is None else _ptr(a)
+        oc, of, hd = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        fi = np.zeros(max(n, 1), np.uint32) if fire else None
+        nf = np.zeros(1, np.uint32) if fire else None
+        self._c(lib.gd_callbacks_respond(self.h, _ptr(i), p(rs), p(rj), p(fl), p(tn), n, _ptr(oc), _ptr(of), _ptr(hd),
+                                         p(fi), p(nf)))
+        return (oc, of, hd, fi[:int(nf[0])].copy()) if fire else (oc, of, hd)
+
+    def _callbacks_scan(self, fn, arg, cap: int):
+        ids, hd, kd = np.zeros(max(cap, 1), np.int64), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint8)
+        n = np.zeros(1, np.uint32)
+        self._c(fn(self.h, arg, cap, _ptr(ids), _ptr(hd), _ptr(kd), _ptr(n)))
+        k = int(n[0])
+        return ids[:k].copy(), hd[:k].copy(), kd[:k].copy()
+
+    def callbacks_expire(self, now: int, cap: int):
+        """gd_callbacks_expire: (id i64, handle u32, kind u8) of the due entries, in no particular order."""
+        return self._callbacks_scan(lib.gd_callbacks_expire, now, cap)
+
+    def callbacks_break_silo(self, silo: int, cap: int):
+        """gd_callbacks_break_silo: (id i64, handle u32, kind u8) of the entries whose target is `silo`."""
+        return self._callbacks_scan(lib.gd_callbacks_break_silo, silo, cap)
+
+    def callbacks_add_device(self, d_ids: int, d_handles: int, d_deadlines: int, n: int, d_out_added: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_add_device(self.h, V(d_ids), V(d_handles), V(d_deadlines), n, V(d_out_added)))
+
+    def callbacks_set_target_device(self, d_ids: int, d_silo: int, n: int, d_out_found: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_set_target_device(self.h, V(d_ids), V(d_silo), n, V(d_out_found)))
+
+    def callbacks_lookup_device(self, d_ids: int, n: int, d_out_handle: Optional[int] = None,
+                                d_out_resend: Optional[int] = None, d_out_silo: Optional[int] = None,
+                                d_out_found: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_lookup_device(self.h, V(d_ids), n, V(d_out_handle), V(d_out_resend), V(d_out_silo),
+                                               V(d_out_found)))
+
+    def callbacks_respond_device(self, d_ids: int, d_result: Optional[int], d_rejection_type: Optional[int],
+                                 d_flags: Optional[int], d_turn: Optional[int], n: int, d_out_outcome: int,
+                                 d_out_flags: int, d_out_handle: int, d_fire_idx: Optional[int] = None,
+                                 d_n_fire: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_respond_device(self.h, V(d_ids), V(d_result), V(d_rejection_type), V(d_flags), V(d_turn),
+                                                n, V(d_out_outcome), V(d_out_flags), V(d_out_handle), V(d_fire_idx),
+                                                V(d_n_fire)))
+
+    def callbacks_expire_device(self, now: int, cap: int, d_out_id: int, d_out_handle: int, d_out_kind: int, d_n_out: int):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_expire_device(self.h, now, cap, V(d_out_id), V(d_out_handle), V(d_out_kind), V(d_n_out)))
+
+    def callbacks_break_silo_device(self, silo: int, cap: int, d_out_id: int, d_out_handle: int, d_out_kind: int,
+                                    d_n_out: int):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_callbacks_break_silo_device(self.h, silo, cap, V(d_out_id), V(d_out_handle), V(d_out_kind),
+                                                   V(d_n_out)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
