@@ -1481,6 +1481,73 @@ int gd_index_stats_get(gd_handle* h, gd_index_stats* out);
 int gd_route_bound_device(gd_handle* h, const gd_key* d_keys, uint32_t n, uint32_t* d_silo, uint32_t* d_act,
                           uint8_t* d_status);
 
+/* ---- frame encoder: Message.SetTargetPlacement + Message.Serialize for a batch -------
+ * The counterpart of gd_decode_frames: the frames of a routed batch leave with their address written.
+ * Per message the reference does two things after AddressMessage found the activation:
+ *   Message.SetTargetPlacement (Message.cs:629-639, from Dispatcher.cs:753-767) sets TargetActivation,
+ *     TargetSilo, IsNewPlacement (only ever to true) and NewGrainType (unless String.IsNullOrEmpty);
+ *   Message.Serialize (Message.cs:481-516, HeadersContainer.Serializer :1126-1245) re-emits
+ *     [int32 headerLength][int32 bodyLength][headers][body].
+ * Here, for input frame i with route outputs silo[i], act[i], status[i]:
+ *   TargetActivation = the ActivationId of act[i] (gd_activation_ids_set) as a UniqueKey: N0, N1,
+ *     TypeCodeData, null KeyExt (int32 -1): 28 B (BinaryTokenStreamWriter.cs:37-49), after SendingSilo and
+ *     before TargetGrain; a TargetActivation already there is replaced, its KeyExt string included.
+ *   TargetSilo = silos[silo[i]] as ip[16], port, generation: 24 B (BinaryTokenStreamWriter.cs:485-513), after
+ *     TargetGrain -- after TargetObserver when that is present, i.e. at the end of the header -- and before
+ *     TransactionInfo; replaced if present.
+ *   IsNewPlacement, when placed[i] == GD_PLACED_NEW: the True token (byte 3) after AlwaysInterleave and
+ *     before ReadOnly; a token already there becomes True.  Any other placed[i] (or placed NULL) leaves the
+ *     frame's own field as it is.
+ *   NewGrainType, when new_type[i] indexes a non-empty string of the configured table: int32 UTF-8 length +
+ *     bytes after IsUnordered and before RejectionInfo; replaced if present.  0xFFFFFFFF, an index >= n_types,
+ *     an empty string or new_type NULL leave the frame's own field as it is.
+ *   The mask gains the bits of the written fields, headerLength is rewritten, bodyLength is not; every other
+ *   byte of the header, and the body, is copied in order.
+ * Encode status, one byte per input frame, decided in this order:
+ *   route status other than GD_ROUTE_OK / GD_ROUTE_ADDRESSED  -> GD_ENC_SKIPPED (a miss has no address; system
+ *     targets need ActivationId.GetSystemActivation, Dispatcher.cs:785-800: both stay in C#)
+ *   the decoder's GD_FRAME_MALFORMED length conditions          -> GD_ENC_MALFORMED
+ *   GD_ROUTE_ADDRESSED (complete address, Dispatcher.cs:718)    -> GD_ENC_COPIED, a byte-for-byte copy
+ *   CacheInvalidationHeader or RequestContext present, or TargetObserver and TransactionInfo both present (an
+ *     insertion point lies behind an object-serialized field)   -> GD_ENC_FALLBACK, C# serializes it
+ *   the header walk runs off the header                          -> GD_ENC_MALFORMED
+ *   silo[i] >= n_silos                                           -> GD_ENC_NO_SILO
+ *   act[i] has no ActivationId (index past the map, or all zero) -> GD_ENC_NO_ID
+ *   else                                                         -> GD_ENC_OK, the patched frame
+ * Only OK and COPIED frames contribute bytes.  Output frame j is input frame order[j] (order: a permutation
+ * of 0..n-1, e.g. gd_send_queues' perm; NULL = batch order): out_off[j] is its first byte in out_buf,
+ * out_off[n] the total, so sender queue q of gd_send_queues owns the bytes
+ * [out_off[offsets[q]], out_off[offsets[q + 1]]) -- one socket write.
+ * Capacity: the total is compared with out_cap on the device.  If it is larger, nothing is written to
+ * out_buf, out_off is still complete (out_off[n] = the size needed) and the handle's device error word is
+ * raised: gd_encode_frames returns GD_EFULL, gd_encode_frames_device reports it at the next checked
+ * synchronisation (as the asynchronous directory batches do).  Frames must be disjoint ranges of buf.
+ * Totals are 32-bit: a call whose bound buf_len + n * (57 + longest configured type string) reaches 2^32 is
+ * refused with GD_EINVAL (no 64-bit scan).  n == 0 is valid and writes out_off[0] = 0.
+ * gd_encode_configure may be repeated; it synchronises the handle first.  type_off[0] = 0, n_types + 1
+ * non-decreasing entries; a type string holds at most 65520 bytes.  The batch calls return GD_ESTATE before
+ * it, and inside a hipGraph capture. */
+#define GD_ENC_OK        0
+#define GD_ENC_COPIED    1
+#define GD_ENC_SKIPPED   2
+#define GD_ENC_FALLBACK  3
+#define GD_ENC_MALFORMED 4
+#define GD_ENC_NO_ID     5
+#define GD_ENC_NO_SILO   6
+#define GD_ENC_NO_TYPE   0xFFFFFFFFu
+int gd_encode_configure(gd_handle* h, const gd_silo_addr* silos, uint32_t n_silos, const uint8_t* type_utf8,
+                        const uint32_t* type_off, uint32_t n_types);
+/* Device pointers, enqueue only, no host read-back.  d_placed, d_new_type, d_order may be NULL. */
+int gd_encode_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                            uint32_t n, const uint32_t* d_silo, const uint32_t* d_act, const uint8_t* d_status,
+                            const uint8_t* d_placed, const uint32_t* d_new_type, const uint32_t* d_order,
+                            uint8_t* d_out_buf, uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_enc_status);
+/* Host pointers, synchronous; *out_total (may be NULL) = out_off[n]. */
+int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                     const uint32_t* silo, const uint32_t* act, const uint8_t* status, const uint8_t* placed,
+                     const uint32_t* new_type, const uint32_t* order, uint8_t* out_buf, uint64_t out_cap,
+                     uint64_t* out_off, uint8_t* enc_status, uint64_t* out_total);
+
 #ifdef __cplusplus
 }
 #endif

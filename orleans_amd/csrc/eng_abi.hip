@@ -121,6 +121,7 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf* b : {&h->cb_tab, &h->cb_dl, &h->cb_ctr, &h->cb_last}) free_buf(*b);
     for (DevBuf& b : h->cb_scr) free_buf(b);
     for (DevBuf& b : h->cb_buf) free_buf(b);
+    encode_release(h);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

@@ -1,0 +1,186 @@
+// eng_encode.hip -- libgraindispatch: the frame encoder: Message.SetTargetPlacement + Message.Serialize
+// for the frames of a routed batch, written in batch order or in a given order (gd_send_queues' perm) as one
+// contiguous byte run (gd_encode.h).
+// Shared handle and helpers: gd_engine.h.
+#include "gd_engine.h"
+#include "gd_encode.h"
+
+namespace {
+
+int check_encode_state(gd_handle* h, const char* call) {
+    if (!h) return set_err(nullptr, GD_ESTATE, "%s: null handle (no gd_encode_configure)", call);
+    if (!h->enc_nsilos) return set_err(h, GD_ESTATE, "%s before gd_encode_configure", call);
+    return GD_OK;
+}
+
+// Refused inside a hipGraph capture (scratch may grow), before anything is launched.
+int check_not_capturing(gd_handle* h, const char* call) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
+    return GD_OK;
+}
+
+// The most bytes the call can write: frames are disjoint ranges of buf, and a frame grows by at most
+// 28 (TargetActivation) + 24 (TargetSilo) + 1 (IsNewPlacement) + 4 + the longest type string.  Totals are
+// 32-bit (gd_encode.h): a bound of 2^32 or more is refused.
+int encode_bound(gd_handle* h, uint64_t buf_len, uint32_t n, uint64_t* bound) {
+    *bound = buf_len + (uint64_t)n * (57ull + h->enc_maxtype);
+    if (buf_len >= (1ull << 32) || *bound >= (1ull << 32))
+        return set_err(h, GD_EINVAL, "encode frames: buf_len + n * (57 + longest type string) reaches 2^32");
+    return GD_OK;
+}
+
+EncTab enc_tab(gd_handle* h) {
+    return EncTab{(const uint64_t*)h->act_ids.p, h->n_act_ids, (const uint32_t*)h->enc_tab[0].p, h->enc_nsilos,
+                  (const uint8_t*)h->enc_tab[1].p, (const uint32_t*)h->enc_tab[2].p, h->enc_ntypes};
+}
+
+// The stage on device arrays (placed / new_type / order may be null); enqueue only.
+int encode_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                  const uint32_t* silo, const uint32_t* act, const uint8_t* status, const uint8_t* placed,
+                  const uint32_t* new_type, const uint32_t* order, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
+                  uint8_t* enc_status, uint64_t bound) {
+    if (n == 0) {
+        HIP_TRY(h, hipMemsetAsync(out_off, 0, sizeof(uint64_t), h->stream));
+        return GD_OK;
+    }
+    StageTime stage(h, "stage:encode");
+    GD_TRY(ensure(h, h->enc_scr[0], (size_t)n * sizeof(EncPlan)));
+    GD_TRY(ensure(h, h->enc_scr[1], (size_t)n * 4));
+    GD_TRY(ensure(h, h->enc_scr[2], ((size_t)n + 1) * 4 + 16));
+    EncPlan* plan = (EncPlan*)h->enc_scr[0].p;
+    uint32_t* lens = (uint32_t*)h->enc_scr[1].p;
+    uint32_t* offs = (uint32_t*)h->enc_scr[2].p;
+    const EncTab t = enc_tab(h);
+    GD_TRY(launch(h, "k_enc_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_enc_plan, buf, buf_len, frame_off, n,
+                  silo, act, status, placed, new_type, t, plan, lens, enc_status));
+    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
+                  (const uint32_t*)lens, order, n, offs));
+    GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "encode"));
+    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
+                  (const uint32_t*)offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+    const EncArgs a{buf, frame_off, silo, act, new_type, order, plan, offs, n, out_cap};
+    return launch(h, "k_enc_write", dim3(blocks_for(bound + 16, ENC_TILE_CHUNKS * 16)), dim3(BLOCK), 0, k_enc_write, a, t,
+                  out);
+}
+
+int check_encode_args(gd_handle* h, const void* buf, const void* off, uint32_t n, const void* silo, const void* act,
+                      const void* status, const void* out, uint64_t out_cap, const void* out_off,
+                      const void* enc_status) {
+    if (!out_off) return set_err(h, GD_EINVAL, "null argument");
+    if (n && (!buf || !off || !silo || !act || !status || !enc_status || (!out && out_cap)))
+        return set_err(h, GD_EINVAL, "null argument");
+    if (n > (1u << 31)) return set_err(h, GD_EINVAL, "encode frames: n > 2^31");
+    return GD_OK;
+}
+
+}  // namespace
+
+namespace gdx {
+
+void encode_release(gd_handle* h) {
+    for (DevBuf& b : h->enc_tab) free_buf(b);
+    for (DevBuf& b : h->enc_scr) free_buf(b);
+    for (DevBuf& b : h->enc_buf) free_buf(b);
+}
+
+}  // namespace gdx
+
+extern "C" {
+
+int gd_encode_configure(gd_handle* h, const gd_silo_addr* silos, uint32_t n_silos, const uint8_t* type_utf8,
+                        const uint32_t* type_off, uint32_t n_types) {
+    if (!h || !silos || n_silos < 1) return set_err(h, GD_EINVAL, "gd_encode_configure: null argument or no silo");
+    if (n_types && (!type_off || (type_off[n_types] && !type_utf8)))
+        return set_err(h, GD_EINVAL, "gd_encode_configure: null type table");
+    if (n_types == 0xFFFFFFFFu) return set_err(h, GD_EINVAL, "gd_encode_configure: n_types too large");
+    uint32_t longest = 0;
+    for (uint32_t k = 0; k < n_types; ++k) {
+        if (type_off[k + 1] < type_off[k]) return set_err(h, GD_EINVAL, "gd_encode_configure: type_off decreases at %u", k);
+        longest = std::max(longest, type_off[k + 1] - type_off[k]);
+    }
+    if (n_types && type_off[0] != 0) return set_err(h, GD_EINVAL, "gd_encode_configure: type_off[0] is not 0");
+    if (longest > ENC_MAX_TYPE)
+        return set_err(h, GD_EINVAL, "gd_encode_configure: a type string of %u bytes (at most %u)", longest, ENC_MAX_TYPE);
+    HIP_TRY(h, hipSetDevice(h->device));
+    // the wire SiloAddress: 16-byte IP, int32 port, int32 generation (BinaryTokenStreamWriter.cs:485-513)
+    std::vector<uint32_t> wire((size_t)n_silos * 6);
+    for (uint32_t s = 0; s < n_silos; ++s) {
+        std::memcpy(&wire[(size_t)s * 6], silos[s].ip, 16);
+        wire[(size_t)s * 6 + 4] = (uint32_t)silos[s].port;
+        wire[(size_t)s * 6 + 5] = (uint32_t)silos[s].generation;
+    }
+    const uint32_t zero_off[1] = {0};
+    GD_TRY(sync(h));                               // a batch in flight reads the tables it was enqueued with
+    h->enc_nsilos = 0;
+    GD_TRY(h2d(h, h->enc_tab[0], wire.data(), wire.size()));
+    GD_TRY(h2d(h, h->enc_tab[1], type_utf8, n_types ? (size_t)type_off[n_types] : 0));
+    GD_TRY(h2d(h, h->enc_tab[2], n_types ? type_off : zero_off, (size_t)n_types + 1));
+    GD_TRY(sync(h));
+    h->enc_ntypes = n_types;
+    h->enc_maxtype = longest;
+    h->enc_nsilos = n_silos;
+    return GD_OK;
+}
+
+int gd_encode_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                            uint32_t n, const uint32_t* d_silo, const uint32_t* d_act, const uint8_t* d_status,
+                            const uint8_t* d_placed, const uint32_t* d_new_type, const uint32_t* d_order,
+                            uint8_t* d_out_buf, uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_enc_status) {
+    GD_TRY(check_encode_state(h, "gd_encode_frames_device"));
+    GD_TRY(check_encode_args(h, d_buf, d_frame_off, n, d_silo, d_act, d_status, d_out_buf, out_cap, d_out_off,
+                             d_enc_status));
+    uint64_t bound = 0;
+    GD_TRY(encode_bound(h, buf_len, n, &bound));
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_encode_frames_device"));
+    return encode_device(h, d_buf, buf_len, d_frame_off, n, d_silo, d_act, d_status, d_placed, d_new_type, d_order,
+                         d_out_buf, out_cap, d_out_off, d_enc_status, bound);
+}
+
+int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                     const uint32_t* silo, const uint32_t* act, const uint8_t* status, const uint8_t* placed,
+                     const uint32_t* new_type, const uint32_t* order, uint8_t* out_buf, uint64_t out_cap,
+                     uint64_t* out_off, uint8_t* enc_status, uint64_t* out_total) {
+    GD_TRY(check_encode_state(h, "gd_encode_frames"));
+    GD_TRY(check_encode_args(h, buf, frame_off, n, silo, act, status, out_buf, out_cap, out_off, enc_status));
+    uint64_t bound = 0;
+    GD_TRY(encode_bound(h, buf_len, n, &bound));
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_encode_frames"));
+    if (out_total) *out_total = 0;
+    if (n == 0) {
+        out_off[0] = 0;
+        return GD_OK;
+    }
+    DevBuf* B = h->enc_buf;
+    GD_TRY(h2d(h, B[0], buf, (size_t)buf_len));
+    GD_TRY(h2d(h, B[1], frame_off, n));
+    GD_TRY(h2d(h, B[2], silo, n));
+    GD_TRY(h2d(h, B[3], act, n));
+    GD_TRY(h2d(h, B[4], status, n));
+    if (placed) GD_TRY(h2d(h, B[5], placed, n));
+    if (new_type) GD_TRY(h2d(h, B[6], new_type, n));
+    if (order) GD_TRY(h2d(h, B[7], order, n));
+    const uint64_t cap = std::min(out_cap, bound);                 // the total never exceeds the bound
+    GD_TRY(ensure(h, B[8], (size_t)cap + 16));
+    GD_TRY(ensure(h, B[9], ((size_t)n + 1) * 8));
+    GD_TRY(ensure(h, B[10], (size_t)n + 8));
+    GD_TRY(encode_device(h, (const uint8_t*)B[0].p, buf_len, (const uint64_t*)B[1].p, n, (const uint32_t*)B[2].p,
+                         (const uint32_t*)B[3].p, (const uint8_t*)B[4].p, placed ? (const uint8_t*)B[5].p : nullptr,
+                         new_type ? (const uint32_t*)B[6].p : nullptr, order ? (const uint32_t*)B[7].p : nullptr,
+                         (uint8_t*)B[8].p, cap, (uint64_t*)B[9].p, (uint8_t*)B[10].p, bound));
+    GD_TRY(d2h(h, out_off, B[9], (size_t)n + 1));
+    GD_TRY(d2h(h, enc_status, B[10], n));
+    GD_TRY(sync(h));
+    const uint64_t total = out_off[n];
+    if (out_total) *out_total = total;
+    if (total && total <= cap)
+        HIP_TRY(h, hipMemcpyAsync(out_buf, B[8].p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+    const int rc = sync_checked(h);                                // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
+    if (rc != GD_OK) return rc;
+    return GD_OK;
+}
+
+}  // extern "C"

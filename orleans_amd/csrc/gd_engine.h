@@ -166,6 +166,13 @@ struct gd_handle {
     DevBuf cb_scr[4];                 // slot_of, is_new / class, fire tile counts, scan flags
     DevBuf cb_buf[16];                // host-pointer entry points: inputs and outputs
 
+    // frame encoder (gd_encode.h, eng_encode.hip): the wire SiloAddress per silo index, the grain-class name
+    // bytes and their offsets (gd_encode_configure)
+    DevBuf enc_tab[3];
+    uint32_t enc_nsilos = 0, enc_ntypes = 0, enc_maxtype = 0;   // enc_nsilos 0: not configured
+    DevBuf enc_scr[3];                // plan records, output lengths, scanned offsets
+    DevBuf enc_buf[11];               // host-pointer entry point: inputs and outputs
+
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
     uint64_t kx_cap = 0;
@@ -477,6 +484,7 @@ int receive_device(gd_handle* h, const gd_key* tg, const gd_key* ta, const uint8
 int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
                           uint32_t n_ctx, const gd_recv_limits* lim, const gd_frame_fields* out, uint32_t* ctx,
                           uint8_t* st, uint32_t* perm, uint32_t* offsets);
+void encode_release(gd_handle* h);
 int grow(gd_handle* h, DevBuf& b, size_t bytes);
 int comm_setup(gd_handle* h);
 int kx_rehash(gd_handle* h, uint64_t cap);

@@ -38,6 +38,8 @@ CB_NONE, CB_FIRE, CB_RESEND, CB_NO_CALLBACK, CB_GATEWAY_BACK, CB_TIMEOUT, CB_SIL
 CB_INVALIDATE_CACHE = 1
 RESP_TARGET_NOT_ME, RESP_HAS_CACHE_HEADER = 1, 2
 CB_NO_SILO = 0xFFFFFFFF
+ENC_OK, ENC_COPIED, ENC_SKIPPED, ENC_FALLBACK, ENC_MALFORMED, ENC_NO_ID, ENC_NO_SILO = range(7)
+ENC_NO_TYPE = 0xFFFFFFFF
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -87,6 +89,7 @@ EXPORTED_SYMBOLS = [
     "gd_callbacks_add", "gd_callbacks_set_target_device", "gd_callbacks_set_target", "gd_callbacks_lookup_device",
     "gd_callbacks_lookup", "gd_callbacks_respond_device", "gd_callbacks_respond", "gd_callbacks_expire_device",
     "gd_callbacks_expire", "gd_callbacks_break_silo_device", "gd_callbacks_break_silo",
+    "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
 ]
 
 
@@ -330,6 +333,9 @@ def _load() -> C.CDLL:
         "gd_callbacks_expire": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
         "gd_callbacks_break_silo_device": (C.c_int, [P, U32, U32, P, P, P, P]),
         "gd_callbacks_break_silo": (C.c_int, [P, U32, U32, P, P, P, P]),
+        "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
+        "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
+        "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -1729,6 +1735,48 @@ class GrainDispatch:
         self._c(lib.gd_route_frames_device(self.h, C.c_void_p(d_buf), buf_len, C.c_void_p(d_offsets), n, n_act,
                                            C.byref(ff), C.c_void_p(d_silo), C.c_void_p(d_act), C.c_void_p(d_status),
                                            C.c_void_p(d_perm or 0), C.c_void_p(d_offs or 0)))
+
+    # -- frame encoder (Message.SetTargetPlacement + Message.Serialize) -----------------
+    def encode_configure(self, silos: Sequence[Tuple[str, int, int]], type_names: Sequence[str] = ()):
+        """gd_encode_configure: silos[s] = (ip, port, generation) of silo index s; type_names[t] = the
+        grain-class name new_type index t stands for."""
+        arr = (gd_silo_addr * len(silos))(*[silo_addr(*s) for s in silos])
+        blobs = [t.encode("utf-8") for t in type_names]
+        off = np.zeros(len(blobs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+        utf8 = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
+        self._c(lib.gd_encode_configure(self.h, arr, len(silos), _ptr(utf8), _ptr(off), len(blobs)))
+
+    def encode_frames(self, buf: bytes, offsets, silo, act, status, placed=None, new_type=None, order=None,
+                      out_cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """gd_encode_frames: (out bytes u8[out_cap], out_off u64[n + 1], enc_status u8[n], total).  `out`: a
+        caller's u8 array to write into (its length is out_cap)."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        s = np.ascontiguousarray(np.asarray(silo, dtype=np.uint32))
+        a = np.ascontiguousarray(np.asarray(act, dtype=np.uint32))
+        st = np.ascontiguousarray(np.asarray(status, dtype=np.uint8))
+        pl, nt, od = self._opt(placed, np.uint8), self._opt(new_type, np.uint32), self._opt(order, np.uint32)
+        if out is None:
+            out = np.zeros(len(buf) + n * 128 if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        est = np.zeros(n, np.uint8)
+        total = C.c_uint64(0)
+        self._c(lib.gd_encode_frames(self.h, _ptr(b), len(buf), _ptr(off), n, _ptr(s), _ptr(a), _ptr(st),
+                                     None if pl is None else _ptr(pl), None if nt is None else _ptr(nt),
+                                     None if od is None else _ptr(od), _ptr(out) if len(out) else None, len(out),
+                                     _ptr(out_off), _ptr(est), C.byref(total)))
+        return out, out_off, est, int(total.value)
+
+    def encode_frames_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, d_silo: int, d_act: int,
+                             d_status: int, d_placed: Optional[int], d_new_type: Optional[int],
+                             d_order: Optional[int], d_out: int, out_cap: int, d_out_off: int, d_enc_status: int):
+        self._c(lib.gd_encode_frames_device(self.h, C.c_void_p(d_buf), buf_len, C.c_void_p(d_offsets), n,
+                                            C.c_void_p(d_silo), C.c_void_p(d_act), C.c_void_p(d_status),
+                                            C.c_void_p(d_placed or 0), C.c_void_p(d_new_type or 0),
+                                            C.c_void_p(d_order or 0), C.c_void_p(d_out), out_cap,
+                                            C.c_void_p(d_out_off), C.c_void_p(d_enc_status)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
