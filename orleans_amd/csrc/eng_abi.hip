@@ -109,19 +109,16 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->shard_hist);
     free_buf(h->send_tab);
     for (DevBuf& b : h->send_scr) free_buf(b);
-    for (DevBuf& b : h->send_buf) free_buf(b);
     free_buf(h->place_sorted);
     free_buf(h->place_compat);
     for (DevBuf& b : h->place_scr) free_buf(b);
-    for (DevBuf& b : h->place_buf) free_buf(b);
     for (DevBuf& b : h->turn_scr) free_buf(b);
-    for (DevBuf& b : h->turn_buf) free_buf(b);
     for (DevBuf& b : h->pump_scr) free_buf(b);
-    for (DevBuf& b : h->pump_buf) free_buf(b);
     for (DevBuf* b : {&h->cb_tab, &h->cb_dl, &h->cb_ctr, &h->cb_last}) free_buf(*b);
     for (DevBuf& b : h->cb_scr) free_buf(b);
-    for (DevBuf& b : h->cb_buf) free_buf(b);
-    encode_release(h);
+    for (DevBuf& b : h->enc_tab) free_buf(b);
+    for (DevBuf& b : h->enc_scr) free_buf(b);
+    for (DevBuf& b : h->stage_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);
     if (h->kx_slots) (void)hipFree(h->kx_slots);

@@ -20,23 +20,6 @@ int check_handle(gd_handle* h, const char* call, uint64_t n = 0) {
     return GD_OK;
 }
 
-// Refused inside a hipGraph capture: the call needs a read-back.
-int check_not_capturing(gd_handle* h, const char* call) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
-    return GD_OK;
-}
-
-// `words` u32 words at device address p, read back (synchronises the stream).
-int read_words(gd_handle* h, const void* p, uint32_t* out, size_t words) {
-    GD_TRY(pinned_scratch(h, words * 4));
-    HIP_TRY(h, hipMemcpyAsync(h->h_pin, p, words * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    memcpy(out, h->h_pin, words * 4);
-    return GD_OK;
-}
-
 struct CbCounts {
     uint32_t live, tomb, err;
 };
@@ -44,14 +27,12 @@ struct CbCounts {
 // The counters after a synchronisation (live / tomb summed over their stripes); device error bits are cleared
 // and reported once.
 int cb_pull(gd_handle* h, CbCounts* c, const char* call) {
-    GD_TRY(pinned_scratch(h, sizeof(CbCounters)));
-    HIP_TRY(h, hipMemcpyAsync(h->h_pin, h->cb_ctr.p, sizeof(CbCounters), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    const CbCounters* full = (const CbCounters*)h->h_pin;
-    *c = CbCounts{0, 0, full->err};
+    CbCounters full;
+    GD_TRY(read_back(h, h->cb_ctr.p, (uint32_t*)&full, sizeof(CbCounters) / 4));
+    *c = CbCounts{0, 0, full.err};
     for (uint32_t k = 0; k < CB_STRIPES; ++k) {
-        c->live += full->stripe[k][0];
-        c->tomb += full->stripe[k][1];
+        c->live += full.stripe[k][0];
+        c->tomb += full.stripe[k][1];
     }
     if (!c->err) return GD_OK;
     CbCounters* d = (CbCounters*)h->cb_ctr.p;
@@ -146,7 +127,7 @@ int add_device(gd_handle* h, const int64_t* ids, const uint32_t* handles, const 
     if (sync_passes) {
         for (uint32_t p = 1;; ++p) {
             uint32_t deferred = 0;
-            GD_TRY(read_words(h, &t.ctr->retry[(p - 1) % CB_PASSES], &deferred, 1));
+            GD_TRY(read_back(h, &t.ctr->retry[(p - 1) % CB_PASSES], &deferred, 1));
             if (!deferred) break;
             if (p > 4096) return set_err(h, GD_ETIMEOUT, "%s: the claims did not settle", call);
             HIP_TRY(h, hipMemsetAsync(&t.ctr->retry[p % CB_PASSES], 0, 4, h->stream));
@@ -201,7 +182,7 @@ int respond_device(gd_handle* h, const CbResp& a, uint32_t n, uint32_t* fire_idx
     if (max_resend && sync_rounds) {
         for (uint32_t r = 1;; ++r) {
             uint32_t unresolved = 0;
-            GD_TRY(read_words(h, &t.ctr->unres[(r - 1) % CB_ROUNDS], &unresolved, 1));
+            GD_TRY(read_back(h, &t.ctr->unres[(r - 1) % CB_ROUNDS], &unresolved, 1));
             if (!unresolved) break;
             if (r > max_resend + 2u) return set_err(h, GD_ETIMEOUT, "%s: the rounds did not settle", call);
             HIP_TRY(h, hipMemsetAsync(&t.ctr->unres[r % CB_ROUNDS], 0, 4, h->stream));
@@ -257,29 +238,20 @@ int scan_apply_host(gd_handle* h, uint32_t by_silo, int64_t now, uint32_t silo, 
     GD_TRY(check_not_capturing(h, call));
     // a list never holds more than the table: outputs of that size stand in for a larger cap
     const uint32_t dcap = (uint32_t)std::min<uint64_t>(cap, h->cb_cap);
-    DevBuf* B = h->cb_buf;
-    GD_TRY(ensure(h, B[8], (size_t)dcap * 8 + 8));
-    GD_TRY(ensure(h, B[9], (size_t)dcap * 4 + 4));
-    GD_TRY(ensure(h, B[10], (size_t)dcap + 16));
-    GD_TRY(ensure(h, B[11], 4));
-    GD_TRY(scan_apply_device(h, by_silo, now, silo, dcap, (int64_t*)B[8].p, (uint32_t*)B[9].p, (uint8_t*)B[10].p,
-                             (uint32_t*)B[11].p));
-    GD_TRY(read_words(h, B[11].p, n_out, 1));
+    HostStage io(h);
+    int64_t* did = io.hold<int64_t>(dcap, 8);          // the first *n_out of the three come down, once it is known
+    uint32_t* dhandle = io.hold<uint32_t>(dcap, 4);
+    uint8_t* dkind = io.hold<uint8_t>(dcap, 16);
+    uint32_t* dn = io.hold<uint32_t>(1);
+    GD_TRY(io.status());
+    GD_TRY(scan_apply_device(h, by_silo, now, silo, dcap, did, dhandle, dkind, dn));
+    GD_TRY(read_back(h, dn, n_out, 1));
     if (*n_out > cap) return set_err(h, GD_EINVAL, "%s: %u entries are due, cap is %u (nothing changed)", call, *n_out, cap);
-    GD_TRY(d2h(h, out_id, B[8], *n_out));
-    GD_TRY(d2h(h, out_handle, B[9], *n_out));
-    GD_TRY(d2h(h, out_kind, B[10], *n_out));
+    GD_TRY(io.fetch(out_id, did, *n_out));
+    GD_TRY(io.fetch(out_handle, dhandle, *n_out));
+    GD_TRY(io.fetch(out_kind, dkind, *n_out));
     CbCounts c;
     return cb_pull(h, &c, call);
-}
-
-template <typename T>
-int up(gd_handle* h, DevBuf& b, const T* src, size_t count, const T** d) {
-    *d = nullptr;
-    if (!src) return GD_OK;
-    GD_TRY(h2d(h, b, src, count));
-    *d = (const T*)b.p;
-    return GD_OK;
 }
 
 }  // namespace
@@ -353,15 +325,14 @@ int gd_callbacks_add(gd_handle* h, const int64_t* ids, const uint32_t* handles, 
     if (n && (!ids || !handles || !deadlines)) return set_err(h, GD_EINVAL, "gd_callbacks_add: null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_callbacks_add"));
-    DevBuf* B = h->cb_buf;
-    const int64_t *di, *dd;
-    const uint32_t* dh;
-    GD_TRY(up(h, B[0], ids, n, &di));
-    GD_TRY(up(h, B[1], handles, n, &dh));
-    GD_TRY(up(h, B[2], deadlines, n, &dd));
-    GD_TRY(ensure(h, B[3], (size_t)n + 16));
-    GD_TRY(add_device(h, di, dh, dd, n, (uint8_t*)B[3].p, true, "gd_callbacks_add"));
-    GD_TRY(d2h(h, out_added, B[3], n));
+    HostStage io(h);
+    const int64_t* di = io.in(ids, n);
+    const uint32_t* dh = io.in(handles, n);
+    const int64_t* dd = io.in(deadlines, n);
+    uint8_t* dadded = io.out(out_added, n, 16);
+    GD_TRY(io.status());
+    GD_TRY(add_device(h, di, dh, dd, n, dadded, true, "gd_callbacks_add"));
+    GD_TRY(io.fetch());
     CbCounts c;
     return cb_pull(h, &c, "gd_callbacks_add");
 }
@@ -382,14 +353,13 @@ int gd_callbacks_set_target(gd_handle* h, const int64_t* ids, const uint32_t* si
             return set_err(h, GD_EINVAL, "gd_callbacks_set_target: silo index above 0xFFFE at %u", i);
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_callbacks_set_target"));
-    DevBuf* B = h->cb_buf;
-    const int64_t* di;
-    const uint32_t* ds;
-    GD_TRY(up(h, B[0], ids, n, &di));
-    GD_TRY(up(h, B[1], silo, n, &ds));
-    GD_TRY(ensure(h, B[3], (size_t)n + 16));
-    GD_TRY(set_target_device(h, di, ds, n, (uint8_t*)B[3].p));
-    GD_TRY(d2h(h, out_found, B[3], n));
+    HostStage io(h);
+    const int64_t* di = io.in(ids, n);
+    const uint32_t* ds = io.in(silo, n);
+    uint8_t* dfound = io.out(out_found, n, 16);
+    GD_TRY(io.status());
+    GD_TRY(set_target_device(h, di, ds, n, dfound));
+    GD_TRY(io.fetch());
     CbCounts c;
     return cb_pull(h, &c, "gd_callbacks_set_target");
 }
@@ -408,18 +378,15 @@ int gd_callbacks_lookup(gd_handle* h, const int64_t* ids, uint32_t n, uint32_t* 
     if (n && !ids) return set_err(h, GD_EINVAL, "gd_callbacks_lookup: null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_callbacks_lookup"));
-    DevBuf* B = h->cb_buf;
-    const int64_t* di;
-    GD_TRY(up(h, B[0], ids, n, &di));
-    GD_TRY(ensure(h, B[4], (size_t)n * 4 + 4));
-    GD_TRY(ensure(h, B[5], (size_t)n * 4 + 4));
-    GD_TRY(ensure(h, B[6], (size_t)n * 4 + 4));
-    GD_TRY(ensure(h, B[3], (size_t)n + 16));
-    GD_TRY(lookup_device(h, di, n, (uint32_t*)B[4].p, (uint32_t*)B[5].p, (uint32_t*)B[6].p, (uint8_t*)B[3].p));
-    GD_TRY(d2h(h, out_handle, B[4], n));
-    GD_TRY(d2h(h, out_resend, B[5], n));
-    GD_TRY(d2h(h, out_silo, B[6], n));
-    GD_TRY(d2h(h, out_found, B[3], n));
+    HostStage io(h);
+    const int64_t* di = io.in(ids, n);
+    uint32_t* dhandle = io.out(out_handle, n, 4);
+    uint32_t* dresend = io.out(out_resend, n, 4);
+    uint32_t* dsilo = io.out(out_silo, n, 4);
+    uint8_t* dfound = io.out(out_found, n, 16);
+    GD_TRY(io.status());
+    GD_TRY(lookup_device(h, di, n, dhandle, dresend, dsilo, dfound));
+    GD_TRY(io.fetch());
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return GD_OK;
 }
@@ -448,35 +415,22 @@ int gd_callbacks_respond(gd_handle* h, const int64_t* ids, const uint8_t* result
         return set_err(h, GD_EINVAL, "gd_callbacks_respond: null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_callbacks_respond"));
-    DevBuf* B = h->cb_buf;
+    HostStage io(h);
     CbResp a{};
-    GD_TRY(up(h, B[0], ids, n, &a.ids));
-    GD_TRY(up(h, B[1], result, n, &a.result));
-    GD_TRY(up(h, B[2], rejection_type, n, &a.rejection));
-    GD_TRY(up(h, B[12], flags, n, &a.flags));
-    GD_TRY(up(h, B[13], turn, n, &a.turn));
-    GD_TRY(ensure(h, B[3], (size_t)n + 16));
-    GD_TRY(ensure(h, B[14], (size_t)n + 16));
-    GD_TRY(ensure(h, B[4], (size_t)n * 4 + 4));
-    a.outcome = (uint8_t*)B[3].p;
-    a.oflags = (uint8_t*)B[14].p;
-    a.handle = (uint32_t*)B[4].p;
-    uint32_t *dfire = nullptr, *dnf = nullptr;
-    if (fire_idx) {
-        GD_TRY(ensure(h, B[5], (size_t)n * 4 + 4));
-        GD_TRY(ensure(h, B[11], 4));
-        dfire = (uint32_t*)B[5].p;
-        dnf = (uint32_t*)B[11].p;
-    }
+    a.ids = io.in(ids, n);
+    a.result = io.in(result, n);
+    a.rejection = io.in(rejection_type, n);
+    a.flags = io.in(flags, n);
+    a.turn = io.in(turn, n);
+    a.outcome = io.out(out_outcome, n, 16);
+    a.oflags = io.out(out_flags, n, 16);
+    a.handle = io.out(out_handle, n, 4);
+    // the whole fire list comes down (n entries at most); the host reads the first *n_fire
+    uint32_t* dfire = io.out_if(fire_idx, n, 4);
+    uint32_t* dnf = io.out_if(n_fire, 1);
+    GD_TRY(io.status());
     GD_TRY(respond_device(h, a, n, dfire, dnf, true, "gd_callbacks_respond"));
-    GD_TRY(d2h(h, out_outcome, B[3], n));
-    GD_TRY(d2h(h, out_flags, B[14], n));
-    GD_TRY(d2h(h, out_handle, B[4], n));
-    if (fire_idx) {
-        // the whole list comes down (n entries at most); the host reads the first *n_fire
-        GD_TRY(d2h(h, fire_idx, B[5], n));
-        GD_TRY(d2h(h, n_fire, B[11], 1));
-    }
+    GD_TRY(io.fetch());
     CbCounts c;
     return cb_pull(h, &c, "gd_callbacks_respond");
 }

@@ -473,6 +473,24 @@ int pinned_scratch(gd_handle* h, size_t bytes) {
     return GD_OK;
 }
 
+// A call that reads back, grows scratch or times its variants is refused inside a hipGraph capture, before
+// anything is launched.
+int check_not_capturing(gd_handle* h, const char* call) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
+    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
+    return GD_OK;
+}
+
+// `words` u32 words at device address d through the pinned scratch; the stream is idle on return.
+int read_back(gd_handle* h, const void* d, uint32_t* out, size_t words) {
+    GD_TRY(pinned_scratch(h, words * 4));
+    HIP_TRY(h, hipMemcpyAsync(h->h_pin, d, words * 4, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    memcpy(out, h->h_pin, words * 4);
+    return GD_OK;
+}
+
 // The device error bits of the last counter read-back (pull_counters) as the call's result: cleared on
 // the device, so each error is reported once.
 int report_device_error(gd_handle* h) {

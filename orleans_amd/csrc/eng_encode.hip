@@ -13,14 +13,6 @@ int check_encode_state(gd_handle* h, const char* call) {
     return GD_OK;
 }
 
-// Refused inside a hipGraph capture (scratch may grow), before anything is launched.
-int check_not_capturing(gd_handle* h, const char* call) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
-    return GD_OK;
-}
-
 // The most bytes the call can write: frames are disjoint ranges of buf, and a frame grows by at most
 // 28 (TargetActivation) + 24 (TargetSilo) + 1 (IsNewPlacement) + 4 + the longest type string.  Totals are
 // 32-bit (gd_encode.h): a bound of 2^32 or more is refused.
@@ -76,16 +68,6 @@ int check_encode_args(gd_handle* h, const void* buf, const void* off, uint32_t n
 }
 
 }  // namespace
-
-namespace gdx {
-
-void encode_release(gd_handle* h) {
-    for (DevBuf& b : h->enc_tab) free_buf(b);
-    for (DevBuf& b : h->enc_scr) free_buf(b);
-    for (DevBuf& b : h->enc_buf) free_buf(b);
-}
-
-}  // namespace gdx
 
 extern "C" {
 
@@ -154,30 +136,28 @@ int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const u
         out_off[0] = 0;
         return GD_OK;
     }
-    DevBuf* B = h->enc_buf;
-    GD_TRY(h2d(h, B[0], buf, (size_t)buf_len));
-    GD_TRY(h2d(h, B[1], frame_off, n));
-    GD_TRY(h2d(h, B[2], silo, n));
-    GD_TRY(h2d(h, B[3], act, n));
-    GD_TRY(h2d(h, B[4], status, n));
-    if (placed) GD_TRY(h2d(h, B[5], placed, n));
-    if (new_type) GD_TRY(h2d(h, B[6], new_type, n));
-    if (order) GD_TRY(h2d(h, B[7], order, n));
     const uint64_t cap = std::min(out_cap, bound);                 // the total never exceeds the bound
-    GD_TRY(ensure(h, B[8], (size_t)cap + 16));
-    GD_TRY(ensure(h, B[9], ((size_t)n + 1) * 8));
-    GD_TRY(ensure(h, B[10], (size_t)n + 8));
-    GD_TRY(encode_device(h, (const uint8_t*)B[0].p, buf_len, (const uint64_t*)B[1].p, n, (const uint32_t*)B[2].p,
-                         (const uint32_t*)B[3].p, (const uint8_t*)B[4].p, placed ? (const uint8_t*)B[5].p : nullptr,
-                         new_type ? (const uint32_t*)B[6].p : nullptr, order ? (const uint32_t*)B[7].p : nullptr,
-                         (uint8_t*)B[8].p, cap, (uint64_t*)B[9].p, (uint8_t*)B[10].p, bound));
-    GD_TRY(d2h(h, out_off, B[9], (size_t)n + 1));
-    GD_TRY(d2h(h, enc_status, B[10], n));
+    HostStage io(h);
+    const uint8_t* dbuf = io.in(buf, (size_t)buf_len);
+    const uint64_t* dfoff = io.in(frame_off, n);
+    const uint32_t* dsilo = io.in(silo, n);
+    const uint32_t* dact = io.in(act, n);
+    const uint8_t* dstatus = io.in(status, n);
+    const uint8_t* dplaced = io.in(placed, n);
+    const uint32_t* dtype = io.in(new_type, n);
+    const uint32_t* dorder = io.in(order, n);
+    uint8_t* dout = io.hold<uint8_t>((size_t)cap, 16);           // out_off[n] bytes come down, once that is known
+    uint64_t* dooff = io.out(out_off, (size_t)n + 1);
+    uint8_t* denc = io.out(enc_status, n, 8);
+    GD_TRY(io.status());
+    GD_TRY(encode_device(h, dbuf, buf_len, dfoff, n, dsilo, dact, dstatus, dplaced, dtype, dorder, dout, cap, dooff,
+                         denc, bound));
+    GD_TRY(io.fetch());
     GD_TRY(sync(h));
     const uint64_t total = out_off[n];
     if (out_total) *out_total = total;
     if (total && total <= cap)
-        HIP_TRY(h, hipMemcpyAsync(out_buf, B[8].p, (size_t)total, hipMemcpyDeviceToHost, h->stream));
+        GD_TRY(io.fetch(out_buf, dout, (size_t)total));
     const int rc = sync_checked(h);                                // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
     if (rc != GD_OK) return rc;
     return GD_OK;

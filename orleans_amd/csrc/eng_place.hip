@@ -22,23 +22,6 @@ int check_place_state(gd_handle* h, const char* call) {
     return GD_OK;
 }
 
-// Refused inside a hipGraph capture (the call reads back), before anything is launched.
-int check_not_capturing(gd_handle* h, const char* call) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
-    return GD_OK;
-}
-
-// One u32 from the device through the pinned scratch; the stream is idle on return.
-int read_word(gd_handle* h, const uint32_t* d, uint32_t* out) {
-    GD_TRY(pinned_scratch(h, sizeof(uint32_t)));
-    HIP_TRY(h, hipMemcpyAsync(h->h_pin, d, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    *out = *(const uint32_t*)h->h_pin;
-    return GD_OK;
-}
-
 // The route, then the placement of its misses, on device arrays (strategy / given / new_idx may be null).
 // *n_new / *n_prop are host words.  A batch without a candidate costs the mark, the scan and one read-back.
 int place_device(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* strategy, uint32_t default_strategy,
@@ -61,7 +44,7 @@ int place_device(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* st
                   strategy, default_strategy, given, n, a, tiles, wide, placed, tile_cnt));
     GD_TRY(scan_device<OpAdd>(h, tile_cnt, tiles + 1, false, false, "place"));
     uint32_t m = 0;
-    GD_TRY(read_word(h, tile_cnt + tiles, &m));
+    GD_TRY(read_back(h, tile_cnt + tiles, &m, 1));
     if (m == 0) return GD_OK;
     if ((uint64_t)act_base + m > (uint64_t)GD_ACT_MULTI)
         return set_err(h, GD_EINVAL, "route place: act_base %u + %u proposals reaches GD_ACT_MULTI", act_base, m);
@@ -89,44 +72,39 @@ int place_device(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* st
     if (new_idx)
         GD_TRY(launch(h, "k_place_new", dim3(blocks), dim3(PL_NT), 0, k_place_new, (const uint32_t*)idx,
                       (const gd_val*)win, (const uint8_t*)ins, m, (const uint32_t*)blk_cnt, new_idx, n));
-    GD_TRY(read_word(h, blk_cnt + blocks, n_new));
+    GD_TRY(read_back(h, blk_cnt + blocks, n_new, 1));
     *n_prop = m;
     return GD_OK;
 }
 
 struct PlaceHost {
-    const uint8_t* strategy = nullptr;
-    const uint32_t* given = nullptr;
+    const uint8_t* strategy;
+    const uint32_t* given;
+    uint8_t* placed;
+    uint32_t* new_idx;
 };
 
-// Host-pointer forms: keys and the optional inputs up.
-int place_inputs(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* strategy, const uint32_t* given,
-                 bool want_new, PlaceHost* d) {
+// Host-pointer forms: keys and the optional inputs up, room for the outputs (silo / act / status: out_a..c).
+int place_inputs(gd_handle* h, HostStage& io, const gd_key* keys, uint32_t n, const uint8_t* strategy,
+                 const uint32_t* given, uint8_t* out_placed, bool want_new, PlaceHost* d) {
     GD_TRY(h2d(h, h->keys_in, keys, n));
-    if (strategy) {
-        GD_TRY(h2d(h, h->place_buf[0], strategy, n));
-        d->strategy = (const uint8_t*)h->place_buf[0].p;
-    }
-    if (given) {
-        GD_TRY(h2d(h, h->place_buf[1], given, n));
-        d->given = (const uint32_t*)h->place_buf[1].p;
-    }
+    d->strategy = io.in(strategy, n);
+    d->given = io.in(given, n);
     GD_TRY(ensure(h, h->out_a, (size_t)n * 4 + 4));
     GD_TRY(ensure(h, h->out_b, (size_t)n * 4 + 4));
     GD_TRY(ensure(h, h->out_c, (size_t)n + 4));
-    GD_TRY(ensure(h, h->place_buf[2], (size_t)n + 4));
-    if (want_new) GD_TRY(ensure(h, h->place_buf[3], (size_t)n * 4 + 4));
-    return GD_OK;
+    d->placed = io.out(out_placed, n, 4);
+    d->new_idx = io.hold<uint32_t>(n, 4, want_new);   // the first n_new come down (place_outputs)
+    return io.status();
 }
 
-int place_outputs(gd_handle* h, uint32_t n, uint32_t n_new, uint32_t* out_silo, uint32_t* out_act, uint8_t* out_status,
-                  uint8_t* out_placed, uint32_t* out_new_idx) {
+int place_outputs(gd_handle* h, HostStage& io, const PlaceHost& d, uint32_t n, uint32_t n_new, uint32_t* out_silo,
+                  uint32_t* out_act, uint8_t* out_status, uint32_t* out_new_idx) {
     GD_TRY(d2h(h, out_silo, h->out_a, n));
     GD_TRY(d2h(h, out_act, h->out_b, n));
     GD_TRY(d2h(h, out_status, h->out_c, n));
-    GD_TRY(d2h(h, out_placed, h->place_buf[2], n));
-    if (out_new_idx) GD_TRY(d2h(h, out_new_idx, h->place_buf[3], n_new));
-    return GD_OK;
+    GD_TRY(io.fetch());
+    return io.fetch(out_new_idx, d.new_idx, n_new);
 }
 
 }  // namespace
@@ -185,13 +163,13 @@ int gd_route_place(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* 
         return set_err(h, GD_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_route_place"));
+    HostStage io(h);
     PlaceHost d;
-    GD_TRY(place_inputs(h, keys, n, strategy, given_silo, out_new_idx != nullptr, &d));
+    GD_TRY(place_inputs(h, io, keys, n, strategy, given_silo, out_placed, out_new_idx != nullptr, &d));
     GD_TRY(place_device(h, (const gd_key*)h->keys_in.p, n, d.strategy, (uint32_t)default_strategy, d.given, act_base,
-                        (uint32_t*)h->out_a.p, (uint32_t*)h->out_b.p, (uint8_t*)h->out_c.p,
-                        (uint8_t*)h->place_buf[2].p, out_new_idx ? (uint32_t*)h->place_buf[3].p : nullptr, out_n_new,
-                        out_n_proposed));
-    GD_TRY(place_outputs(h, n, *out_n_new, out_silo, out_act, out_status, out_placed, out_new_idx));
+                        (uint32_t*)h->out_a.p, (uint32_t*)h->out_b.p, (uint8_t*)h->out_c.p, d.placed, d.new_idx,
+                        out_n_new, out_n_proposed));
+    GD_TRY(place_outputs(h, io, d, n, *out_n_new, out_silo, out_act, out_status, out_new_idx));
     return sync_checked(h);
 }
 
@@ -225,16 +203,16 @@ int gd_route_place_bucket(gd_handle* h, const gd_key* keys, uint32_t n, const ui
     if (n_act == 0xFFFFFFFFu) return set_err(h, GD_EINVAL, "n_act too large");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_route_place_bucket"));
+    HostStage io(h);
     PlaceHost d;
-    GD_TRY(place_inputs(h, keys, n, strategy, given_silo, out_new_idx != nullptr, &d));
+    GD_TRY(place_inputs(h, io, keys, n, strategy, given_silo, out_placed, out_new_idx != nullptr, &d));
     GD_TRY(ensure(h, h->u8_a, (size_t)n * 4 + 4));   // perm
     GD_TRY(ensure(h, h->offs, ((size_t)n_act + 2) * 4));
     GD_TRY(place_device(h, (const gd_key*)h->keys_in.p, n, d.strategy, (uint32_t)default_strategy, d.given, act_base,
-                        (uint32_t*)h->out_a.p, (uint32_t*)h->out_b.p, (uint8_t*)h->out_c.p,
-                        (uint8_t*)h->place_buf[2].p, out_new_idx ? (uint32_t*)h->place_buf[3].p : nullptr, out_n_new,
-                        out_n_proposed));
+                        (uint32_t*)h->out_a.p, (uint32_t*)h->out_b.p, (uint8_t*)h->out_c.p, d.placed, d.new_idx,
+                        out_n_new, out_n_proposed));
     GD_TRY(bucket_device(h, (const uint32_t*)h->out_b.p, n, n_act, (uint32_t*)h->u8_a.p, (uint32_t*)h->offs.p));
-    GD_TRY(place_outputs(h, n, *out_n_new, out_silo, out_act, out_status, out_placed, out_new_idx));
+    GD_TRY(place_outputs(h, io, d, n, *out_n_new, out_silo, out_act, out_status, out_new_idx));
     GD_TRY(d2h(h, out_perm, h->u8_a, n));
     GD_TRY(d2h(h, out_offsets, h->offs, (size_t)n_act + 2));
     return sync_checked(h);

@@ -45,14 +45,6 @@ int check_merge_args(gd_handle* h, const gd_wait_list* old_list, uint32_t n_ctx,
     return GD_OK;
 }
 
-// Refused inside a hipGraph capture (the bucketing times its variants), before anything is launched.
-int check_not_capturing(gd_handle* h, const char* call) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
-    return GD_OK;
-}
-
 // The completion stage on device arrays.
 int complete_device(gd_handle* h, const uint32_t* done_ctx, const uint8_t* done_flags, uint32_t n_done, uint32_t n_ctx,
                     const uint8_t* ctx_flags, const uint32_t* num_running, const uint32_t* woff, const uint8_t* wflags,
@@ -121,15 +113,6 @@ int merge_device(gd_handle* h, const MergeArgs& a, uint32_t* off_out, uint32_t* 
                   flags_out, total);
 }
 
-template <typename T>
-int up(gd_handle* h, DevBuf& b, const T* src, size_t count, const T** d) {
-    *d = nullptr;
-    if (!src) return GD_OK;
-    GD_TRY(h2d(h, b, src, count));
-    *d = (const T*)b.p;
-    return GD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -160,45 +143,27 @@ int gd_turns_complete(gd_handle* h, const uint32_t* done_ctx, const uint8_t* don
     if (total > wait_cap) return set_err(h, GD_EINVAL, "wait list longer than wait_cap");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_turns_complete"));
-    DevBuf* B = h->pump_buf;
-    const uint32_t *dctx, *dnr, *dwoff;
-    const uint8_t *ddf, *dfl, *dwf;
-    GD_TRY(up(h, B[0], done_ctx, n_done, &dctx));
-    GD_TRY(up(h, B[1], done_flags, n_done, &ddf));
-    GD_TRY(up(h, B[2], ctx_flags, n_ctx, &dfl));
-    GD_TRY(up(h, B[3], num_running, n_ctx, &dnr));
-    GD_TRY(up(h, B[4], n_ctx ? wait->offsets : nullptr, (size_t)n_ctx + 1, &dwoff));
-    GD_TRY(up(h, B[5], total ? wait->flags : nullptr, total, &dwf));
-    GD_TRY(ensure(h, B[6], (size_t)n_ctx + 16));
-    GD_TRY(ensure(h, B[7], (size_t)n_ctx * 4 + 4));
-    GD_TRY(ensure(h, B[8], (size_t)n_ctx * 4 + 4));
-    GD_TRY(ensure(h, B[9], (size_t)n_ctx * 4 + 4));
-    GD_TRY(ensure(h, B[10], (size_t)n_ctx + 16));
-    PumpOut o{(uint8_t*)B[6].p, (uint32_t*)B[7].p, (uint32_t*)B[8].p, (uint32_t*)B[9].p, (uint8_t*)B[10].p,
-              nullptr,          nullptr,           nullptr};
-    if (out_n_started_by) {
-        GD_TRY(ensure(h, B[11], (size_t)n_done * 4 + 4));
-        o.n_started_by = (uint32_t*)B[11].p;
-    }
-    if (out_start_pos) {
-        GD_TRY(ensure(h, B[12], (size_t)total * 4 + 4));
-        GD_TRY(ensure(h, B[13], 4));
-        o.start_pos = (uint32_t*)B[12].p;
-        o.n_start = (uint32_t*)B[13].p;
-    }
+    HostStage io(h);
+    const uint32_t* dctx = io.in(done_ctx, n_done);
+    const uint8_t* ddf = io.in(done_flags, n_done);
+    const uint8_t* dfl = io.in(ctx_flags, n_ctx);
+    const uint32_t* dnr = io.in(num_running, n_ctx);
+    const uint32_t* dwoff = io.in(n_ctx ? wait->offsets : nullptr, (size_t)n_ctx + 1);
+    const uint8_t* dwf = io.in(total ? wait->flags : nullptr, total);
+    PumpOut o;
+    o.ctx_flags = io.out(out_ctx_flags, n_ctx, 16);
+    o.num_running = io.out(out_num_running, n_ctx, 4);
+    o.n_dequeued = io.out(out_n_dequeued, n_ctx, 4);
+    o.running_pos = io.out(out_running_pos, n_ctx, 4);
+    o.event = io.out(out_event, n_ctx, 16);
+    o.n_started_by = io.out_if(out_n_started_by, n_done, 4);
+    // the whole start list comes down (offsets[n_ctx] entries at most); the host reads the first *out_n_start
+    o.start_pos = io.out_if(out_start_pos, total, 4);
+    o.n_start = io.out_if(out_n_start, 1);
+    GD_TRY(io.status());
     // the list's own length is the device form's capacity: nothing past it can start
     GD_TRY(complete_device(h, dctx, ddf, n_done, n_ctx, dfl, dnr, dwoff, dwf, total, o));
-    GD_TRY(d2h(h, out_ctx_flags, B[6], n_ctx));
-    GD_TRY(d2h(h, out_num_running, B[7], n_ctx));
-    GD_TRY(d2h(h, out_n_dequeued, B[8], n_ctx));
-    GD_TRY(d2h(h, out_running_pos, B[9], n_ctx));
-    GD_TRY(d2h(h, out_event, B[10], n_ctx));
-    if (out_n_started_by) GD_TRY(d2h(h, out_n_started_by, B[11], n_done));
-    if (out_start_pos) {
-        // the whole list comes down (offsets[n_ctx] entries at most); the host reads the first *out_n_start
-        GD_TRY(d2h(h, out_start_pos, B[12], total));
-        GD_TRY(d2h(h, out_n_start, B[13], 1));
-    }
+    GD_TRY(io.fetch());
     return sync_checked(h);
 }
 
@@ -242,35 +207,34 @@ int gd_wait_list_merge(gd_handle* h, const gd_wait_list* old_list, const uint32_
     const uint32_t old_total = old ? old_list->offsets[n_ctx] : 0u;
     // the new list holds at most the old entries and the batch: a device capacity past that changes nothing
     const uint32_t dcap = (uint32_t)std::min<uint64_t>(cap, (uint64_t)old_total + n);
-    DevBuf* B = h->pump_buf;
+    const bool chain = allow_call_chain_reentrancy && target_activation;
+    HostStage io(h);
     MergeArgs a{};
-    GD_TRY(up(h, B[14], old ? old_list->offsets : nullptr, (size_t)n_ctx + 1, &a.old_off));
-    GD_TRY(up(h, B[15], old ? old_list->msg : nullptr, old_total, &a.old_msg));
-    GD_TRY(up(h, B[16], old ? old_list->flags : nullptr, old_total, &a.old_flags));
-    GD_TRY(up(h, B[17], old ? n_dequeued : nullptr, n_ctx, &a.n_deq));
-    GD_TRY(up(h, B[18], wait_perm, n, &a.wperm));
-    GD_TRY(up(h, B[19], wait_offsets, (size_t)n_ctx + 2, &a.woff));
-    GD_TRY(up(h, B[20], msg_id, n, &a.msg_id));
-    GD_TRY(up(h, B[21], msg_flags, n, &a.msg_flags));
-    if (allow_call_chain_reentrancy && target_activation) {
-        GD_TRY(up(h, B[22], target_activation, n, &a.ta));
-        GD_TRY(up(h, B[23], sending_activation, n, &a.sa));
-    }
+    a.old_off = io.in(old ? old_list->offsets : nullptr, (size_t)n_ctx + 1);
+    a.old_msg = io.in(old ? old_list->msg : nullptr, old_total);
+    a.old_flags = io.in(old ? old_list->flags : nullptr, old_total);
+    a.n_deq = io.in(old ? n_dequeued : nullptr, n_ctx);
+    a.wperm = io.in(wait_perm, n);
+    a.woff = io.in(wait_offsets, (size_t)n_ctx + 2);
+    a.msg_id = io.in(msg_id, n);
+    a.msg_flags = io.in(msg_flags, n);
+    a.ta = io.in(chain ? target_activation : nullptr, n);
+    a.sa = io.in(chain ? sending_activation : nullptr, n);
     a.n = n;
     a.n_ctx = n_ctx;
     a.id_base = id_base;
     a.cap = dcap;
-    GD_TRY(ensure(h, B[24], ((size_t)n_ctx + 1) * 4));
-    GD_TRY(ensure(h, B[25], (size_t)dcap * 4 + 4));
-    GD_TRY(ensure(h, B[26], (size_t)dcap + 16));
-    GD_TRY(ensure(h, B[27], 4));
-    GD_TRY(merge_device(h, a, (uint32_t*)B[24].p, (uint32_t*)B[25].p, (uint8_t*)B[26].p, (uint32_t*)B[27].p));
-    GD_TRY(d2h(h, out_offsets, B[24], (size_t)n_ctx + 1));
-    GD_TRY(d2h(h, out_total, B[27], 1));
+    uint32_t* doff = io.out(out_offsets, (size_t)n_ctx + 1);
+    uint32_t* dmsg = io.hold<uint32_t>(dcap, 4);       // the first min(total, dcap) come down, once the total is known
+    uint8_t* dflags = io.hold<uint8_t>(dcap, 16);
+    uint32_t* dtotal = io.out(out_total, 1);
+    GD_TRY(io.status());
+    GD_TRY(merge_device(h, a, doff, dmsg, dflags, dtotal));
+    GD_TRY(io.fetch());
     GD_TRY(sync_checked(h));
     const uint32_t keep = std::min(*out_total, dcap);
-    GD_TRY(d2h(h, out_msg, B[25], keep));
-    GD_TRY(d2h(h, out_flags, B[26], keep));
+    GD_TRY(io.fetch(out_msg, dmsg, keep));
+    GD_TRY(io.fetch(out_flags, dflags, keep));
     return sync_checked(h);
 }
 

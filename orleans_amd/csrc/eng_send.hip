@@ -54,40 +54,21 @@ int send_device(gd_handle* h, const uint32_t* silo, const uint8_t* rs, const uin
                   h->lane_order ? h->radix_rank_atomic : 0u);
 }
 
-// Host-pointer forms: the send stage's optional inputs up, its outputs down.  silo / rs: device arrays.
-int send_host(gd_handle* h, const uint32_t* d_silo, const uint8_t* d_rs, const uint8_t* category, const int64_t* ttl,
-              uint32_t n, uint8_t* out_st, uint32_t* out_q, uint32_t* out_perm, uint32_t* out_offsets) {
+// Host-pointer forms: the send stage's optional inputs up, its outputs down, on the caller's staging (which may
+// hold the caller's own arrays ahead of these).  silo / rs: device arrays.
+int send_host(gd_handle* h, HostStage& io, const uint32_t* d_silo, const uint8_t* d_rs, const uint8_t* category,
+              const int64_t* ttl, uint32_t n, uint8_t* out_st, uint32_t* out_q, uint32_t* out_perm,
+              uint32_t* out_offsets) {
     const uint32_t B = h->send_nq + 4;
-    const uint8_t* dcat = nullptr;
-    const int64_t* dttl = nullptr;
-    if (category) {
-        GD_TRY(h2d(h, h->send_buf[2], category, n));
-        dcat = (const uint8_t*)h->send_buf[2].p;
-    }
-    if (ttl) {
-        GD_TRY(h2d(h, h->send_buf[3], ttl, n));
-        dttl = (const int64_t*)h->send_buf[3].p;
-    }
-    GD_TRY(ensure(h, h->send_buf[4], (size_t)n + 4));
-    uint32_t *dq = nullptr, *dperm = nullptr, *doff = nullptr;
-    if (out_q) {
-        GD_TRY(ensure(h, h->send_buf[5], (size_t)n * 4 + 4));
-        dq = (uint32_t*)h->send_buf[5].p;
-    }
-    if (out_perm) {
-        GD_TRY(ensure(h, h->send_buf[6], (size_t)n * 4 + 4));
-        GD_TRY(ensure(h, h->send_buf[7], ((size_t)B + 1) * 4));
-        dperm = (uint32_t*)h->send_buf[6].p;
-        doff = (uint32_t*)h->send_buf[7].p;
-    }
-    GD_TRY(send_device(h, d_silo, d_rs, dcat, dttl, n, (uint8_t*)h->send_buf[4].p, dq, dperm, doff));
-    GD_TRY(d2h(h, out_st, h->send_buf[4], n));
-    if (out_q) GD_TRY(d2h(h, out_q, h->send_buf[5], n));
-    if (out_perm) {
-        GD_TRY(d2h(h, out_perm, h->send_buf[6], n));
-        GD_TRY(d2h(h, out_offsets, h->send_buf[7], (size_t)B + 1));
-    }
-    return GD_OK;
+    const uint8_t* dcat = io.in(category, n);
+    const int64_t* dttl = io.in(ttl, n);
+    uint8_t* dst = io.out(out_st, n, 4);
+    uint32_t* dq = io.out_if(out_q, n, 4);
+    uint32_t* dperm = io.out_if(out_perm, n, 4);
+    uint32_t* doff = io.out_if(out_offsets, (size_t)B + 1);
+    GD_TRY(io.status());
+    GD_TRY(send_device(h, d_silo, d_rs, dcat, dttl, n, dst, dq, dperm, doff));
+    return io.fetch();
 }
 
 }  // namespace
@@ -133,14 +114,10 @@ int gd_send_queues(gd_handle* h, const uint32_t* silo, const uint8_t* route_stat
     GD_TRY(check_send_state(h, "gd_send_queues"));
     if (n && (!silo || !out_send_status)) return set_err(h, GD_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
-    GD_TRY(h2d(h, h->send_buf[0], silo, n));
-    const uint8_t* drs = nullptr;
-    if (route_status) {
-        GD_TRY(h2d(h, h->send_buf[1], route_status, n));
-        drs = (const uint8_t*)h->send_buf[1].p;
-    }
-    GD_TRY(send_host(h, (const uint32_t*)h->send_buf[0].p, drs, category, ttl, n, out_send_status, out_queue, out_perm,
-                     out_offsets));
+    HostStage io(h);
+    const uint32_t* dsilo = io.in(silo, n);
+    const uint8_t* drs = io.in(route_status, n);
+    GD_TRY(send_host(h, io, dsilo, drs, category, ttl, n, out_send_status, out_queue, out_perm, out_offsets));
     return sync(h);
 }
 
@@ -170,8 +147,9 @@ int gd_route_send(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* c
     if (n)
         GD_TRY(route_device(h, (const gd_key*)h->keys_in.p, n, (uint32_t*)h->out_a.p, (uint32_t*)h->out_b.p,
                             (uint8_t*)h->out_c.p));
-    GD_TRY(send_host(h, (const uint32_t*)h->out_a.p, (const uint8_t*)h->out_c.p, category, ttl, n, out_send_status,
-                     out_queue, out_perm, out_offsets));
+    HostStage io(h);
+    GD_TRY(send_host(h, io, (const uint32_t*)h->out_a.p, (const uint8_t*)h->out_c.p, category, ttl, n,
+                     out_send_status, out_queue, out_perm, out_offsets));
     GD_TRY(d2h(h, out_silo, h->out_a, n));
     GD_TRY(d2h(h, out_act, h->out_b, n));
     GD_TRY(d2h(h, out_status, h->out_c, n));

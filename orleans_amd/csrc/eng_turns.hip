@@ -31,14 +31,6 @@ int check_turn_args(gd_handle* h, const void* ta, const void* sa, bool fused, ui
     return GD_OK;
 }
 
-// Refused inside a hipGraph capture (the bucketing times its variants), before anything is launched.
-int check_not_capturing(gd_handle* h, const char* call) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    HIP_TRY(h, hipStreamIsCapturing(h->stream, &cs));
-    if (cs != hipStreamCaptureStatusNone) return set_err(h, GD_ESTATE, "%s inside a stream capture", call);
-    return GD_OK;
-}
-
 // The turn stage on device arrays (state's arrays device memory).
 int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uint8_t* dir, const int64_t* ttl,
                  const uint8_t* fwd, const uint8_t* mf, const gd_key* ta, const gd_key* sa, uint32_t n, uint32_t n_ctx,
@@ -92,15 +84,6 @@ int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uin
     return GD_OK;
 }
 
-template <typename T>
-int up(gd_handle* h, DevBuf& b, const T* src, size_t count, const T** d) {
-    *d = nullptr;
-    if (!src) return GD_OK;
-    GD_TRY(h2d(h, b, src, count));
-    *d = (const T*)b.p;
-    return GD_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -130,53 +113,31 @@ int gd_turns(gd_handle* h, const uint32_t* ctx, const uint8_t* recv_status, cons
     if (n && !ctx) return set_err(h, GD_EINVAL, "null argument");
     HIP_TRY(h, hipSetDevice(h->device));
     GD_TRY(check_not_capturing(h, "gd_turns"));
-    DevBuf* B = h->turn_buf;
-    const uint32_t* dctx;
-    const uint8_t *drs, *ddir, *dfwd, *dmf;
-    const int64_t* dttl;
-    const gd_key *dta, *dsa;
-    GD_TRY(h2d(h, B[0], ctx, n));
-    dctx = (const uint32_t*)B[0].p;
-    GD_TRY(up(h, B[1], recv_status, n, &drs));
-    GD_TRY(up(h, B[2], direction, n, &ddir));
-    GD_TRY(up(h, B[3], ttl, n, &dttl));
-    GD_TRY(up(h, B[4], forward_count, n, &dfwd));
-    GD_TRY(up(h, B[5], msg_flags, n, &dmf));
-    GD_TRY(up(h, B[6], target_activation, n, &dta));
-    GD_TRY(up(h, B[7], sending_activation, n, &dsa));
+    HostStage io(h);
+    const uint32_t* dctx = io.in(ctx, n);
+    const uint8_t* drs = io.in(recv_status, n);
+    const uint8_t* ddir = io.in(direction, n);
+    const int64_t* dttl = io.in(ttl, n);
+    const uint8_t* dfwd = io.in(forward_count, n);
+    const uint8_t* dmf = io.in(msg_flags, n);
+    const gd_key* dta = io.in(target_activation, n);
+    const gd_key* dsa = io.in(sending_activation, n);
     gd_turn_state ds = *state;
-    GD_TRY(up(h, B[8], state->ctx_flags, n_ctx, &ds.ctx_flags));
-    GD_TRY(up(h, B[9], state->num_running, n_ctx, &ds.num_running));
-    GD_TRY(up(h, B[10], state->request_count, n_ctx, &ds.request_count));
-    GD_TRY(ensure(h, B[11], (size_t)n + 16));
-    GD_TRY(ensure(h, B[12], (size_t)n_ctx * 4 + 4));
-    GD_TRY(ensure(h, B[13], (size_t)n_ctx * 4 + 4));
-    TurnOut o{(uint8_t*)B[11].p, (uint32_t*)B[12].p, (uint32_t*)B[13].p, nullptr, nullptr, nullptr, nullptr};
-    if (out_start_idx) {
-        GD_TRY(ensure(h, B[14], (size_t)n * 4 + 4));
-        GD_TRY(ensure(h, B[15], 4));
-        o.start_idx = (uint32_t*)B[14].p;
-        o.n_start = (uint32_t*)B[15].p;
-    }
-    if (out_wait_perm) {
-        GD_TRY(ensure(h, B[16], (size_t)n * 4 + 4));
-        GD_TRY(ensure(h, B[17], ((size_t)n_ctx + 2) * 4));
-        o.wait_perm = (uint32_t*)B[16].p;
-        o.wait_offsets = (uint32_t*)B[17].p;
-    }
+    ds.ctx_flags = io.in(state->ctx_flags, n_ctx);
+    ds.num_running = io.in(state->num_running, n_ctx);
+    ds.request_count = io.in(state->request_count, n_ctx);
+    TurnOut o;
+    o.turn = io.out(out_turn, n, 16);
+    o.num_running = io.out(out_num_running, n_ctx, 4);
+    o.running_idx = io.out(out_running_idx, n_ctx, 4);
+    // the whole start list comes down (n entries at most); the host reads the first *out_n_start
+    o.start_idx = io.out_if(out_start_idx, n, 4);
+    o.n_start = io.out_if(out_n_start, 1);
+    o.wait_perm = io.out_if(out_wait_perm, n, 4);
+    o.wait_offsets = io.out_if(out_wait_offsets, (size_t)n_ctx + 2);
+    GD_TRY(io.status());
     GD_TRY(turns_device(h, dctx, drs, ddir, dttl, dfwd, dmf, dta, dsa, n, n_ctx, &ds, o));
-    GD_TRY(d2h(h, out_turn, B[11], n));
-    GD_TRY(d2h(h, out_num_running, B[12], n_ctx));
-    GD_TRY(d2h(h, out_running_idx, B[13], n_ctx));
-    if (out_start_idx) {
-        // the whole list comes down (n entries at most); the host reads the first *out_n_start
-        GD_TRY(d2h(h, out_start_idx, B[14], n));
-        GD_TRY(d2h(h, out_n_start, B[15], 1));
-    }
-    if (out_wait_perm) {
-        GD_TRY(d2h(h, out_wait_perm, B[16], n));
-        GD_TRY(d2h(h, out_wait_offsets, B[17], (size_t)n_ctx + 2));
-    }
+    GD_TRY(io.fetch());
     return sync_checked(h);
 }
 

@@ -137,7 +137,6 @@ struct gd_handle {
     DevBuf send_tab;
     uint32_t send_nsilos = 0, send_nq = 0;   // 0: not configured
     DevBuf send_scr[2];               // (bucket, tile) counts + totals; bucket ids when the caller wants none
-    DevBuf send_buf[8];               // host-pointer entry points: inputs and outputs
 
     // placement of unregistered grains (gd_place.h, eng_place.hip): the compatible silos in
     // SiloAddress.CompareTo order and their bitset (gd_place_configure)
@@ -145,15 +144,12 @@ struct gd_handle {
     uint32_t place_nsilos = 0, place_ncomp = 0;   // place_nsilos 0: not configured
     bool place_local = false;         // the local silo is active, in the table and compatible
     DevBuf place_scr[7];              // tile counts, block counts; candidates' idx, keys, vals, winners, inserted
-    DevBuf place_buf[4];              // host-pointer entry points: strategy, given silo, placed, new_idx
 
     // turn admission (gd_turns.h, eng_turns.hip)
     DevBuf turn_scr[6];               // tile counts; rank key, perm, offsets, rank (limits); wait-list key
-    DevBuf turn_buf[18];              // host-pointer entry points: inputs, context state, outputs
 
     // turn completion and message pump, wait-list merge (gd_pump.h, eng_pump.hip)
     DevBuf pump_scr[6];               // completions' perm, offsets; start counts, first positions; work list, its count
-    DevBuf pump_buf[28];              // host-pointer entry points: completion (0-13) and merge (14-27) inputs, outputs
 
     // callback table (gd_callbacks.h, eng_callbacks.hip): CorrelationId -> callback handle, resend count, target silo
     DevBuf cb_tab, cb_dl, cb_ctr;     // the 16-B slots, their deadlines, CbCounters
@@ -164,14 +160,20 @@ struct gd_handle {
     bool cb_resend_on_timeout = false;
     int64_t cb_period = 0;
     DevBuf cb_scr[4];                 // slot_of, is_new / class, fire tile counts, scan flags
-    DevBuf cb_buf[16];                // host-pointer entry points: inputs and outputs
 
     // frame encoder (gd_encode.h, eng_encode.hip): the wire SiloAddress per silo index, the grain-class name
     // bytes and their offsets (gd_encode_configure)
     DevBuf enc_tab[3];
     uint32_t enc_nsilos = 0, enc_ntypes = 0, enc_maxtype = 0;   // enc_nsilos 0: not configured
     DevBuf enc_scr[3];                // plan records, output lengths, scanned offsets
-    DevBuf enc_buf[11];               // host-pointer entry point: inputs and outputs
+
+    // The host-pointer forms of the six stages above stage their inputs and outputs here, through HostStage
+    // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
+    // One pool serves them all: each of these calls synchronises the stream before it returns and none reads
+    // what an earlier one staged; a call that returned early on an error left its work on the same stream,
+    // ahead of the next call's, and ensure() synchronises before it frees a slot to grow it.
+    static constexpr uint32_t STAGE_SLOTS = 18;
+    DevBuf stage_buf[STAGE_SLOTS];
 
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
     KxSlot* kx_slots = nullptr;
@@ -422,6 +424,8 @@ int bucket_device(gd_handle* h, const uint32_t* acts, uint32_t n, uint32_t n_act
                   uint32_t* rank_out = nullptr);
 int sync(gd_handle* h);
 int pinned_scratch(gd_handle* h, size_t bytes);
+int check_not_capturing(gd_handle* h, const char* call);
+int read_back(gd_handle* h, const void* d, uint32_t* out, size_t words);
 int sync_checked(gd_handle* h);
 int report_device_error(gd_handle* h);
 int maybe_grow_table(gd_handle* h, uint64_t incoming);
@@ -484,7 +488,6 @@ int receive_device(gd_handle* h, const gd_key* tg, const gd_key* ta, const uint8
 int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
                           uint32_t n_ctx, const gd_recv_limits* lim, const gd_frame_fields* out, uint32_t* ctx,
                           uint8_t* st, uint32_t* perm, uint32_t* offsets);
-void encode_release(gd_handle* h);
 int grow(gd_handle* h, DevBuf& b, size_t bytes);
 int comm_setup(gd_handle* h);
 int kx_rehash(gd_handle* h, uint64_t cap);
@@ -608,5 +611,76 @@ int d2h(gd_handle* h, T* dst, const DevBuf& b, size_t count) {
     if (count && dst) HIP_TRY(h, hipMemcpyAsync(dst, b.p, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
     return GD_OK;
 }
+
+// The staging of one host-pointer call through the handle's stage_buf pool: inputs up, outputs down.
+//   * Slots are positional: the k-th in / out / out_if / hold of a call takes slot k, whether or not an
+//     optional array is there, so calls that toggle optional arrays reuse the same allocations.  More than
+//     STAGE_SLOTS arrays in a call is GD_ESTATE.
+//   * A slot holds at least count * sizeof(T) + pad bytes: pad is the tail a kernel's wide accesses may
+//     touch past count, and each call states its own.
+//   * Nothing here synchronises: in() and fetch() enqueue copies on the handle's stream, and the entry point
+//     ends as it chooses (sync, sync_checked, a counter read-back).
+// After a failure every later in / out / hold gives null and enqueues nothing; status() is the first failure.
+struct HostStage {
+    gd_handle* h;
+    int rc = GD_OK;
+    uint32_t used = 0, n_down = 0;
+    struct Down {
+        void* dst;
+        const void* src;
+        size_t bytes;
+    } down[gd_handle::STAGE_SLOTS];
+
+    explicit HostStage(gd_handle* hh) : h(hh) {}
+
+    // The next slot; null for an absent array (want false) and after a failure.
+    DevBuf* take(bool want) {
+        const uint32_t k = used++;
+        if (rc != GD_OK || !want) return nullptr;
+        if (k < gd_handle::STAGE_SLOTS) return &h->stage_buf[k];
+        rc = set_err(h, GD_ESTATE, "host staging: more than %u arrays in one call", gd_handle::STAGE_SLOTS);
+        return nullptr;
+    }
+    // src's count elements on the device; a null src gives null and copies nothing.
+    template <typename T>
+    const T* in(const T* src, size_t count) {
+        DevBuf* b = take(src != nullptr);
+        if (b) rc = h2d(h, *b, src, count);
+        return b && rc == GD_OK ? (const T*)b->p : nullptr;
+    }
+    // A device array that fetch() leaves alone: the call brings down what it needs of it, fetch(dst, d, count).
+    template <typename T>
+    T* hold(size_t count, size_t pad = 0, bool want = true) {
+        DevBuf* b = take(want);
+        if (b) rc = ensure(h, *b, count * sizeof(T) + pad);
+        return b && rc == GD_OK ? (T*)b->p : nullptr;
+    }
+    // A device array whose first count elements fetch() brings down to dst (a null dst: nowhere).
+    template <typename T>
+    T* out(T* dst, size_t count, size_t pad = 0) {
+        T* d = hold<T>(count, pad);
+        if (d && dst && count) down[n_down++] = Down{dst, d, count * sizeof(T)};
+        return d;
+    }
+    // out() for an optional output: a null dst takes the slot, allocates nothing and gives null.
+    template <typename T>
+    T* out_if(T* dst, size_t count, size_t pad = 0) {
+        return dst ? out(dst, count, pad) : hold<T>(0, 0, false);
+    }
+    int status() const { return rc; }
+    // Enqueue the copies out() remembered, in slot order.
+    int fetch() {
+        for (uint32_t i = 0; i < n_down; ++i)
+            HIP_TRY(h, hipMemcpyAsync(down[i].dst, down[i].src, down[i].bytes, hipMemcpyDeviceToHost, h->stream));
+        n_down = 0;
+        return GD_OK;
+    }
+    // Enqueue one copy of count elements from a device array of this call.
+    template <typename T>
+    int fetch(T* dst, const void* d, size_t count) {
+        if (count && dst) HIP_TRY(h, hipMemcpyAsync(dst, d, count * sizeof(T), hipMemcpyDeviceToHost, h->stream));
+        return GD_OK;
+    }
+};
 
 }  // namespace gdx
