@@ -1084,7 +1084,7 @@ int gd_route_place_bucket(gd_handle* h, const gd_key* keys, uint32_t n, const ui
  * reuse times its variants).
  *
  * Left to C#: deadlock detection (:277-293, off by default), the interface-version check of
- * HandleIncomingRequest (:403-410), TryRescheduleCollection (:118), logging, and the cross-cluster return in
+ * HandleIncomingRequest (:403-410), logging (TryRescheduleCollection, :118: gd_collect_touch*), and the cross-cluster return in
  * TryForwardRequest.  A frame-fed form is not offered: gd_frame_fields has no read-only / interleave / TTL /
  * forward-count outputs, and growing that struct breaks its callers (GD_ABI_VERSION stays 1). */
 #define GD_TURN_NONE              0
@@ -1195,8 +1195,9 @@ int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd
  * n_done == 0 and n_ctx == 0 are valid (context outputs are still written).  n_done <= 2^31.  Enqueue-only on
  * the handle's stream; GD_ESTATE inside a hipGraph capture, as gd_turns_device (it reuses the bucketing).
  *
- * Left to C#: RunningRequestsSenders, the interface-version check of HandleIncomingRequest,
- * TryRescheduleCollection / RunOnInactive (reported through GD_PUMP_BECAME_IDLE), logging. */
+ * Left to C#: RunningRequestsSenders, the interface-version check of HandleIncomingRequest, RunOnInactive
+ * (reported through GD_PUMP_BECAME_IDLE), logging.  (becameIdle and ResetRunning's TryRescheduleCollection:
+ * gd_collect_idle* takes d_event as it is.) */
 #define GD_MSG_CALL_CHAIN         8u
 #define GD_DONE_IS_RUNNING        1u
 #define GD_DONE_PUMP_ONLY         2u
@@ -1240,6 +1241,138 @@ int gd_wait_list_merge(gd_handle* h, const gd_wait_list* old_list, const uint32_
                        uint32_t id_base, const uint8_t* msg_flags, const gd_key* target_activation,
                        const gd_key* sending_activation, int allow_call_chain_reentrancy, uint32_t cap,
                        uint32_t* out_offsets, uint32_t* out_msg, uint8_t* out_flags, uint32_t* out_total);
+
+/* ---- activation collector (Catalog/ActivationCollector.cs, the whole file) ---------------------------
+ * The idle tickets of the activations, the periodic stale scan and the condemned list that feeds
+ * Catalog.DeactivateActivations -> gd_dir_unregister_device / gd_actdir_remove.  The reference keeps a
+ * ConcurrentDictionary<DateTime, Bucket> of ConcurrentDictionary<ActivationId, ActivationData> and takes
+ * lock(activation) per message (TryRescheduleCollection: Core/Dispatcher.cs:116-119, ActivationData.cs:500-507).
+ * Here the collector is two words and a flag byte per context, caller-owned and updated in place (gd_collect_state;
+ * device memory in the *_device forms), and two words on the handle: quantum and nextTicket.
+ *
+ * The invariant that replaces the dictionaries: context c is in bucket ticket[c] iff
+ *     ticket[c] != 0 && !(flags[c] & GD_COL_CANCELLED) && ticket[c] >= nextTicket.
+ * (tests/test_collect_ref.py holds it against a literal dictionary transcription after every step.)
+ *
+ * All times are DateTime.Ticks as int64 (0 < ticks < 2^62); DateTime.UtcNow is the call's `now`, also where the
+ * reference reads the clock twice in one call.  roundup(t) = ((t - 1) / quantum + 1) * quantum
+ * (MakeTicketFromDateTime, :368-377).  A batch gives the results of its items taken one by one in array order.
+ *
+ * gd_collect_configure(quantum_ticks, now): quantum and nextTicket = roundup(now) (:33-37); quantum_ticks <= 0 is
+ *   GD_EINVAL.  Every other gd_collect_* call returns GD_ESTATE before it.  gd_collect_next_ticket reads
+ *   nextTicket.  nextTicket lives on the host side of the handle: the device forms advance it when they enqueue
+ *   (it is a function of `now` alone) and hand the old value to the kernel, so nothing is read back.
+ * schedule = ScheduleCollection (:83-108) per ctx[i], checks in the reference's order: ctx[i] >= n_ctx
+ *   GD_COL_OUT_OF_RANGE; exempt GD_COL_SKIPPED_EXEMPT; age_limit 0 GD_COL_SKIPPED_NO_LIMIT; age_limit < quantum
+ *   GD_COL_THROWS_TIMEOUT (:381); t = roundup(now + age_limit) < nextTicket GD_COL_THROWS_EARLY (:372); ticket != 0
+ *   GD_COL_THROWS_TICKETED (:101); else ticket = t, CANCELLED cleared (Add, :393), GD_COL_SCHEDULED.  Duplicates of
+ *   a context: the first decides; later ones get THROWS_TICKETED if it was scheduled, else its status.
+ * cancel = TryCancelCollection (:110-126): 1 iff not exempt, ticket != 0, ticket >= nextTicket and not CANCELLED;
+ *   then CANCELLED is set and the ticket kept (Bucket.TryRemove).  Duplicates: the first gets 1, later ones 0.
+ * touch = the Dispatcher.cs:116-119 site, fed by gd_receive*'s d_ctx and gd_turns*' turn bytes as they are.
+ *   Message i takes part iff ctx[i] < n_ctx, turn[i] is one of GD_TURN_START, WAIT, REJECT_OVERLOADED, STUCK,
+ *   FORWARD, REJECT_TRANSIENT (a non-expired Request / OneWay that reached ReceiveRequest; NONE, EXPIRED, RESPONSE
+ *   and RESPONSE_DROPPED are out; turn NULL = every message) and ctx_flags[ctx[i]]'s state bits are GD_CTX_VALID.
+ *   Then TryRescheduleCollection (:128-164), literally: exempt GD_COL_FALSE; ticket == 0 FALSE; ticket % quantum
+ *   != 0 GD_COL_THROWS, state unchanged; ticket < nextTicket: ticket = 0, FALSE; age_limit < quantum THROWS;
+ *   t = roundup(now + age_limit) < nextTicket THROWS (:372 again; now far behind nextTicket); t == ticket
+ *   GD_COL_TRUE; CANCELLED: ticket = 0, FALSE; else ticket = t, TRUE.  A message that takes no part:
+ *   GD_COL_NO_PART.  At one `now` the rule is idempotent on a context, so duplicates need no election: every
+ *   occurrence gets the first's answer.
+ * idle = the ResetRunning site, fed by gd_turns_complete*'s event bytes as they are: for every c with event[c] &
+ *   GD_PUMP_BECAME_IDLE: became_idle[c] = now, then touch's rule (exempt: FALSE).  out_ok[n_ctx] optional, NO_PART
+ *   for the others.
+ * scan_stale = ScanStale (:206-264).  With next0 = nextTicket: n_q = next0 > now ? 0 : (now - next0) / quantum + 1
+ *   quanta are dequeued (:166-190) and nextTicket += n_q * quantum; n_q > 2^28 is GD_EINVAL with nothing changed.
+ *   Context c is due iff it is in a bucket, ticket[c] <= now and (ticket[c] - next0) % quantum == 0.  For a due
+ *   context CANCELLED is set (CancelAll) and ticket = 0, then (:219-259), in order:
+ *     state != GD_CTX_VALID                       GD_COL_BAD_STATE   nothing
+ *     keep_alive_until >= now                     GD_COL_KEPT_ALIVE  ScheduleCollection (schedule's rule at now)
+ *     (int32)num_running > 0 or a waiting list    GD_COL_ACTIVE      ScheduleCollection
+ *     now - became_idle < age_limit               GD_COL_NOT_STALE   ScheduleCollection
+ *     otherwise                                   GD_COL_COLLECT     PrepareForDeactivation: the state bits become
+ *                                                                    GD_CTX_NOT_READY, other bits kept; listed
+ *   A verdict whose ScheduleCollection did not add (any status but SCHEDULED; an exception in the reference) gets
+ *   | GD_COL_NOT_ADDED.  A context that is not due is untouched, verdict 0.  out_ctx[0 .. *out_n) = the condemned
+ *   contexts in ascending ticket, then ascending context index.  The reference's order inside one bucket is a
+ *   ConcurrentDictionary enumeration, so unspecified: this order is ours.  Entries at and past *out_n are
+ *   unspecified (out_ctx has n_ctx entries); *out_n is a device word in the device form.  The device form is
+ *   enqueue-only, but with n_q > 1 it orders the list by the bucketing, which times its variants: GD_ESTATE inside
+ *   a hipGraph capture, with nothing changed; it then takes 4 * (n_q + 2) bytes of scratch.
+ * scan_all = ScanAll (:271-325): every context in a bucket gets the same chain's verdict with no re-schedule, the
+ *   last test being now - became_idle >= age_limit_ticks; GD_COL_COLLECT: CANCELLED set, the ticket kept
+ *   (TryRemove, :306), the state bits GD_CTX_NOT_READY, listed in ascending context index.  nextTicket stays.
+ * count_recent = GetNumRecentlyUsed (:58-81, DeploymentLoadPublisher.cs:93): the contexts in a bucket when
+ *   shortest_age_limit == 0, else those with shortest_age_limit - (ticket - now) <= recency.
+ *
+ * ticket, became_idle, age_limit and flags are required when n_ctx > 0; keep_alive_until NULL = never kept alive;
+ * wait_offsets NULL = no waiting lists; the out_status / out_cancelled / out_ok / out_verdict outputs may be NULL.
+ * n == 0 and n_ctx == 0 are valid.  n <= 2^31.
+ *
+ * Left to C#: Debug_OnDecideToCollectActivation, the warnings, ToString, DelayDeactivation (the host writes
+ * keep_alive_until), Catalog.DeactivateActivations and everything after the list. */
+#define GD_COL_EXEMPT             1u  /* flags: IsExemptFromCollection (collector == null), host-set */
+#define GD_COL_CANCELLED          2u  /* flags: collectionCancelledFlag */
+#define GD_COL_SCHEDULED          0
+#define GD_COL_OUT_OF_RANGE       1
+#define GD_COL_SKIPPED_EXEMPT     2
+#define GD_COL_SKIPPED_NO_LIMIT   3
+#define GD_COL_THROWS_TIMEOUT     4
+#define GD_COL_THROWS_EARLY       5
+#define GD_COL_THROWS_TICKETED    6
+#define GD_COL_FALSE              0
+#define GD_COL_TRUE               1
+#define GD_COL_THROWS             2
+#define GD_COL_NO_PART            3
+#define GD_COL_BAD_STATE          1
+#define GD_COL_KEPT_ALIVE         2
+#define GD_COL_ACTIVE             3
+#define GD_COL_NOT_STALE          4
+#define GD_COL_COLLECT            5
+#define GD_COL_NOT_ADDED       0x80
+typedef struct gd_collect_state {
+    int64_t*       ticket;            /* CollectionTicket in ticks; 0 = default(DateTime)               */
+    int64_t*       became_idle;       /* becameIdle                                                     */
+    const int64_t* keep_alive_until;  /* keepAliveUntil (DelayDeactivation, host-written); NULL = never */
+    const int64_t* age_limit;         /* CollectionAgeLimit ticks; 0 = off / not initialised            */
+    uint8_t*       flags;             /* GD_COL_EXEMPT, GD_COL_CANCELLED                                */
+} gd_collect_state;
+int gd_collect_configure(gd_handle* h, int64_t quantum_ticks, int64_t now);
+int gd_collect_next_ticket(gd_handle* h, int64_t* out);
+int gd_collect_schedule_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint32_t* d_ctx,
+                               uint32_t n, int64_t now, uint8_t* d_status);
+int gd_collect_schedule(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint32_t* ctx, uint32_t n,
+                        int64_t now, uint8_t* out_status);
+int gd_collect_cancel_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint32_t* d_ctx,
+                             uint32_t n, uint8_t* d_cancelled);
+int gd_collect_cancel(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint32_t* ctx, uint32_t n,
+                      uint8_t* out_cancelled);
+int gd_collect_touch_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint8_t* d_ctx_flags,
+                            const uint32_t* d_ctx, const uint8_t* d_turn, uint32_t n, int64_t now, uint8_t* d_ok);
+int gd_collect_touch(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint8_t* ctx_flags,
+                     const uint32_t* ctx, const uint8_t* turn, uint32_t n, int64_t now, uint8_t* out_ok);
+int gd_collect_idle_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint8_t* d_event,
+                           int64_t now, uint8_t* d_ok);
+int gd_collect_idle(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, const uint8_t* event, int64_t now,
+                    uint8_t* out_ok);
+int gd_collect_scan_stale_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, uint8_t* d_ctx_flags,
+                                 const uint32_t* d_num_running, const uint32_t* d_wait_offsets, int64_t now,
+                                 uint32_t* d_out_ctx, uint32_t* d_out_n, uint8_t* d_verdict);
+/* Host pointers (the state's arrays too, updated in place; out_n a host word), synchronous; so are the host forms
+ * above and below. */
+int gd_collect_scan_stale(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, uint8_t* ctx_flags,
+                          const uint32_t* num_running, const uint32_t* wait_offsets, int64_t now, uint32_t* out_ctx,
+                          uint32_t* out_n, uint8_t* out_verdict);
+int gd_collect_scan_all_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, uint8_t* d_ctx_flags,
+                               const uint32_t* d_num_running, const uint32_t* d_wait_offsets, int64_t now,
+                               int64_t age_limit_ticks, uint32_t* d_out_ctx, uint32_t* d_out_n, uint8_t* d_verdict);
+int gd_collect_scan_all(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, uint8_t* ctx_flags,
+                        const uint32_t* num_running, const uint32_t* wait_offsets, int64_t now,
+                        int64_t age_limit_ticks, uint32_t* out_ctx, uint32_t* out_n, uint8_t* out_verdict);
+int gd_collect_count_recent_device(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, int64_t now,
+                                   int64_t shortest_age_limit, int64_t recency, uint64_t* d_count);
+int gd_collect_count_recent(gd_handle* h, const gd_collect_state* st, uint32_t n_ctx, int64_t now,
+                            int64_t shortest_age_limit, int64_t recency, uint64_t* out_count);
 
 /* ---- callback table (InsideRuntimeClient.callbacks: SendRequest's TryAdd to ReceiveResponse) ---------
  * The outstanding requests of a silo: InsideRuntimeClient.callbacks, ConcurrentDictionary<CorrelationId,

@@ -118,6 +118,7 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->cb_scr) free_buf(b);
     for (DevBuf& b : h->enc_tab) free_buf(b);
     for (DevBuf& b : h->enc_scr) free_buf(b);
+    for (DevBuf& b : h->col_scr) free_buf(b);
     for (DevBuf& b : h->stage_buf) free_buf(b);
     free_buf(h->up_last);
     comm_release(h);

@@ -167,7 +167,12 @@ struct gd_handle {
     uint32_t enc_nsilos = 0, enc_ntypes = 0, enc_maxtype = 0;   // enc_nsilos 0: not configured
     DevBuf enc_scr[3];                // plan records, output lengths, scanned offsets
 
-    // The host-pointer forms of the six stages above stage their inputs and outputs here, through HostStage
+    // activation collector (gd_collect.h, eng_collect.hip): quantum and nextTicket in ticks (gd_collect_configure)
+    int64_t col_quantum = 0, col_next = 0;   // col_quantum 0: not configured
+    DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller
+                                      // wants none; quantum keys; their bucket offsets
+
+    // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
     // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads
     // what an earlier one staged; a call that returned early on an error left its work on the same stream,

@@ -90,6 +90,10 @@ EXPORTED_SYMBOLS = [
     "gd_callbacks_lookup", "gd_callbacks_respond_device", "gd_callbacks_respond", "gd_callbacks_expire_device",
     "gd_callbacks_expire", "gd_callbacks_break_silo_device", "gd_callbacks_break_silo",
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
+    "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
+    "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
+    "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
+    "gd_collect_scan_all_device", "gd_collect_scan_all", "gd_collect_count_recent_device", "gd_collect_count_recent",
 ]
 
 
@@ -183,9 +187,21 @@ class gd_wait_list(C.Structure):
     _fields_ = [("offsets", C.c_void_p), ("msg", C.c_void_p), ("flags", C.c_void_p)]
 
 
+class gd_collect_state(C.Structure):
+    _fields_ = [("ticket", C.c_void_p), ("became_idle", C.c_void_p), ("keep_alive_until", C.c_void_p),
+                ("age_limit", C.c_void_p), ("flags", C.c_void_p)]
+
+
 MSG_CALL_CHAIN = 8
 DONE_IS_RUNNING, DONE_PUMP_ONLY = 1, 2
 PUMP_BECAME_IDLE, PUMP_RUNNING_CLEARED, PUMP_RUNNING_SET = 1, 2, 4
+# activation collector (gd_collect_*): flag bits; schedule statuses; touch / idle answers; scan verdicts
+GD_COL_EXEMPT, GD_COL_CANCELLED = 1, 2
+(GD_COL_SCHEDULED, GD_COL_OUT_OF_RANGE, GD_COL_SKIPPED_EXEMPT, GD_COL_SKIPPED_NO_LIMIT, GD_COL_THROWS_TIMEOUT,
+ GD_COL_THROWS_EARLY, GD_COL_THROWS_TICKETED) = range(7)
+GD_COL_FALSE, GD_COL_TRUE, GD_COL_THROWS, GD_COL_NO_PART = range(4)
+GD_COL_BAD_STATE, GD_COL_KEPT_ALIVE, GD_COL_ACTIVE, GD_COL_NOT_STALE, GD_COL_COLLECT = range(1, 6)
+GD_COL_NOT_ADDED = 0x80
 
 GD_COMM_ID_BYTES = 128
 GD_ACT_MULTI = 0xFFFFFFFE
@@ -249,6 +265,7 @@ def _load() -> C.CDLL:
         pass
     lib = C.CDLL(LIB_PATH)
     P, U32, U64, I32 = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int32
+    I64, CS = C.c_int64, C.POINTER(gd_collect_state)
     sig = {
         "gd_create": (C.c_int, [C.POINTER(gd_config), C.POINTER(P)]),
         "gd_destroy": (None, [P]),
@@ -336,6 +353,22 @@ def _load() -> C.CDLL:
         "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
         "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
+        "gd_collect_configure": (C.c_int, [P, I64, I64]),
+        "gd_collect_next_ticket": (C.c_int, [P, C.POINTER(I64)]),
+        "gd_collect_schedule_device": (C.c_int, [P, CS, U32, P, U32, I64, P]),
+        "gd_collect_schedule": (C.c_int, [P, CS, U32, P, U32, I64, P]),
+        "gd_collect_cancel_device": (C.c_int, [P, CS, U32, P, U32, P]),
+        "gd_collect_cancel": (C.c_int, [P, CS, U32, P, U32, P]),
+        "gd_collect_touch_device": (C.c_int, [P, CS, U32, P, P, P, U32, I64, P]),
+        "gd_collect_touch": (C.c_int, [P, CS, U32, P, P, P, U32, I64, P]),
+        "gd_collect_idle_device": (C.c_int, [P, CS, U32, P, I64, P]),
+        "gd_collect_idle": (C.c_int, [P, CS, U32, P, I64, P]),
+        "gd_collect_scan_stale_device": (C.c_int, [P, CS, U32, P, P, P, I64, P, P, P]),
+        "gd_collect_scan_stale": (C.c_int, [P, CS, U32, P, P, P, I64, P, P, P]),
+        "gd_collect_scan_all_device": (C.c_int, [P, CS, U32, P, P, P, I64, I64, P, P, P]),
+        "gd_collect_scan_all": (C.c_int, [P, CS, U32, P, P, P, I64, I64, P, P, P]),
+        "gd_collect_count_recent_device": (C.c_int, [P, CS, U32, I64, I64, I64, P]),
+        "gd_collect_count_recent": (C.c_int, [P, CS, U32, I64, I64, I64, P]),
         "gd_dir_upsert": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_lookup": (C.c_int, [P, P, U32, P, P]),
         "gd_dir_clear": (C.c_int, [P]),
@@ -1050,6 +1083,116 @@ class GrainDispatch:
                                               V(d_wait_perm), V(d_wait_offsets), n, V(d_msg_id), id_base, V(d_msg_flags),
                                               V(d_target_activation), V(d_sending_activation), int(chain), cap,
                                               V(d_offsets_out), V(d_msg_out), V(d_flags_out), V(d_total)))
+
+    # -- activation collector (Catalog/ActivationCollector.cs) --------------------------------------
+    def collect_configure(self, quantum_ticks: int, now: int):
+        self._c(lib.gd_collect_configure(self.h, quantum_ticks, now))
+
+    def collect_next_ticket(self) -> int:
+        out = C.c_int64(0)
+        self._c(lib.gd_collect_next_ticket(self.h, C.byref(out)))
+        return out.value
+
+    @staticmethod
+    def collect_state(ticket, became_idle, keep_alive_until, age_limit, flags) -> gd_collect_state:
+        """A gd_collect_state over numpy arrays (int64 / uint8, contiguous: updated in place) or device addresses;
+        keep_alive_until may be None."""
+        p = lambda a: (a or None) if a is None or isinstance(a, int) else _ptr(a)
+        for a, dt in ((ticket, np.int64), (became_idle, np.int64), (keep_alive_until, np.int64), (age_limit, np.int64),
+                      (flags, np.uint8)):
+            assert a is None or isinstance(a, int) or (a.dtype == dt and a.flags.c_contiguous)
+        return gd_collect_state(p(ticket), p(became_idle), p(keep_alive_until), p(age_limit), p(flags))
+
+    def collect_schedule(self, st: gd_collect_state, n_ctx: int, ctx, now: int, status: bool = True):
+        """gd_collect_schedule: status u8[n] (GD_COL_SCHEDULED ...) or None; the state's arrays are updated."""
+        cx = np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        out = np.zeros(len(cx), np.uint8) if status else None
+        self._c(lib.gd_collect_schedule(self.h, C.byref(st), n_ctx, _ptr(cx), len(cx), now,
+                                        None if out is None else _ptr(out)))
+        return out
+
+    def collect_cancel(self, st: gd_collect_state, n_ctx: int, ctx, cancelled: bool = True):
+        cx = np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        out = np.zeros(len(cx), np.uint8) if cancelled else None
+        self._c(lib.gd_collect_cancel(self.h, C.byref(st), n_ctx, _ptr(cx), len(cx), None if out is None else _ptr(out)))
+        return out
+
+    def collect_touch(self, st: gd_collect_state, n_ctx: int, ctx_flags, ctx, now: int, turn=None, ok: bool = True):
+        """gd_collect_touch: ok u8[n] (GD_COL_FALSE / TRUE / THROWS / NO_PART) or None."""
+        cx = np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        cf, tb = self._opt(ctx_flags, np.uint8), self._opt(turn, np.uint8)
+        out = np.zeros(len(cx), np.uint8) if ok else None
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_collect_touch(self.h, C.byref(st), n_ctx, p(cf), _ptr(cx), p(tb), len(cx), now, p(out)))
+        return out
+
+    def collect_idle(self, st: gd_collect_state, n_ctx: int, event, now: int, ok: bool = True):
+        ev = np.ascontiguousarray(np.asarray(event, dtype=np.uint8))
+        out = np.zeros(n_ctx, np.uint8) if ok else None
+        self._c(lib.gd_collect_idle(self.h, C.byref(st), n_ctx, _ptr(ev), now, None if out is None else _ptr(out)))
+        return out
+
+    def _collect_scan(self, fn, st, n_ctx, ctx_flags, num_running, wait_offsets, verdict, *mid):
+        assert ctx_flags.dtype == np.uint8 and ctx_flags.flags.c_contiguous       # updated in place
+        nr, wo = self._opt(num_running, np.uint32), self._opt(wait_offsets, np.uint32)
+        out, out_n = np.zeros(max(n_ctx, 1), np.uint32), np.zeros(1, np.uint32)
+        vd = np.zeros(n_ctx, np.uint8) if verdict else None
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(fn(self.h, C.byref(st), n_ctx, _ptr(ctx_flags), p(nr), p(wo), *mid, _ptr(out), _ptr(out_n), p(vd)))
+        return out[:int(out_n[0])].copy(), vd
+
+    def collect_scan_stale(self, st: gd_collect_state, n_ctx: int, ctx_flags, num_running, now: int, wait_offsets=None,
+                           verdict: bool = True):
+        """gd_collect_scan_stale: (condemned u32[out_n] by ticket then context, verdict u8[n_ctx] or None);
+        ctx_flags (uint8 array) and the state's arrays are updated in place."""
+        return self._collect_scan(lib.gd_collect_scan_stale, st, n_ctx, ctx_flags, num_running, wait_offsets, verdict,
+                                  now)
+
+    def collect_scan_all(self, st: gd_collect_state, n_ctx: int, ctx_flags, num_running, now: int, age_limit_ticks: int,
+                         wait_offsets=None, verdict: bool = True):
+        return self._collect_scan(lib.gd_collect_scan_all, st, n_ctx, ctx_flags, num_running, wait_offsets, verdict,
+                                  now, age_limit_ticks)
+
+    def collect_count_recent(self, st: gd_collect_state, n_ctx: int, now: int, shortest_age_limit: int,
+                             recency: int) -> int:
+        out = np.zeros(1, np.uint64)
+        self._c(lib.gd_collect_count_recent(self.h, C.byref(st), n_ctx, now, shortest_age_limit, recency, _ptr(out)))
+        return int(out[0])
+
+    # the device forms: st over device addresses, every array a device address (None = NULL), enqueue-only
+    def collect_schedule_device(self, st, n_ctx: int, d_ctx, n: int, now: int, d_status=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_schedule_device(self.h, C.byref(st), n_ctx, V(d_ctx), n, now, V(d_status)))
+
+    def collect_cancel_device(self, st, n_ctx: int, d_ctx, n: int, d_cancelled=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_cancel_device(self.h, C.byref(st), n_ctx, V(d_ctx), n, V(d_cancelled)))
+
+    def collect_touch_device(self, st, n_ctx: int, d_ctx_flags, d_ctx, d_turn, n: int, now: int, d_ok=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_touch_device(self.h, C.byref(st), n_ctx, V(d_ctx_flags), V(d_ctx), V(d_turn), n, now,
+                                            V(d_ok)))
+
+    def collect_idle_device(self, st, n_ctx: int, d_event, now: int, d_ok=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_idle_device(self.h, C.byref(st), n_ctx, V(d_event), now, V(d_ok)))
+
+    def collect_scan_stale_device(self, st, n_ctx: int, d_ctx_flags, d_num_running, d_wait_offsets, now: int,
+                                  d_out_ctx, d_out_n, d_verdict=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_scan_stale_device(self.h, C.byref(st), n_ctx, V(d_ctx_flags), V(d_num_running),
+                                                 V(d_wait_offsets), now, V(d_out_ctx), V(d_out_n), V(d_verdict)))
+
+    def collect_scan_all_device(self, st, n_ctx: int, d_ctx_flags, d_num_running, d_wait_offsets, now: int,
+                                age_limit_ticks: int, d_out_ctx, d_out_n, d_verdict=None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_collect_scan_all_device(self.h, C.byref(st), n_ctx, V(d_ctx_flags), V(d_num_running),
+                                               V(d_wait_offsets), now, age_limit_ticks, V(d_out_ctx), V(d_out_n),
+                                               V(d_verdict)))
+
+    def collect_count_recent_device(self, st, n_ctx: int, now: int, shortest_age_limit: int, recency: int, d_count):
+        self._c(lib.gd_collect_count_recent_device(self.h, C.byref(st), n_ctx, now, shortest_age_limit, recency,
+                                                   C.c_void_p(d_count or 0)))
 
     # -- callback table (InsideRuntimeClient.callbacks) --------------------------------------------
     def callbacks_configure(self, capacity_hint: int, max_resend_count: int = 0, resend_on_timeout: bool = False,
