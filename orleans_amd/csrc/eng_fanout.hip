@@ -11,6 +11,10 @@ uint64_t grain_tcd(int32_t type_code) {
     return ((uint64_t)CAT_GRAIN << 56) + ((uint64_t)(int64_t)type_code & 0x00FFFFFFFFFFFFFFull);
 }
 
+// fan[1] of the tiled counting plans: the tiles' u32 sums (k_scan_down's partials), then, 8-B aligned,
+// their u64 sums (k_fan_degree_tiles' part64: what the host reads back and adds up).
+static size_t fan_part64_off(uint32_t nb) { return ((size_t)nb * 4 + 7) & ~(size_t)7; }
+
 // Degrees + inclusive scan into fan[0] (ends); the total message count comes back to the host.
 int fan_count(gd_handle* h, const uint32_t* row_off, uint32_t n_nodes, const uint32_t* frontier, uint32_t nf,
               uint64_t* total) {
@@ -23,25 +27,26 @@ int fan_count(gd_handle* h, const uint32_t* row_off, uint32_t n_nodes, const uin
     if (nb4 <= 2048 || nb16 <= 4096) {
         const bool wide = nb4 > 2048;
         const uint32_t nb = wide ? nb16 : nb4;
-        GD_TRY(ensure(h, h->fan[1], (size_t)nb * 4));
-        GD_TRY(pinned_scratch(h, (size_t)nb * 4));
+        GD_TRY(ensure(h, h->fan[1], fan_part64_off(nb) + (size_t)nb * 8));
+        GD_TRY(pinned_scratch(h, (size_t)nb * 8));
         uint32_t* ends = (uint32_t*)h->fan[0].p;
         uint32_t* part = (uint32_t*)h->fan[1].p;
+        unsigned long long* part64 = (unsigned long long*)((char*)h->fan[1].p + fan_part64_off(nb));
         if (wide) {
             GD_TRY(launch(h, "k_fan_degree", dim3(nb), dim3(BLOCK), 0, k_fan_degree_tiles<16>, row_off, n_nodes, frontier,
-                          nf, ends, part, (const uint32_t*)nullptr));
+                          nf, ends, part, part64, (const uint32_t*)nullptr));
             GD_TRY(launch(h, "k_scan_down", dim3(nb), dim3(BLOCK), 0, k_scan_down<OpAdd, 16>, (const uint32_t*)ends, ends,
                           nf, false, true, (const uint32_t*)part, nb));
         } else {
             GD_TRY(launch(h, "k_fan_degree", dim3(nb), dim3(BLOCK), 0, k_fan_degree_tiles<4>, row_off, n_nodes, frontier,
-                          nf, ends, part, (const uint32_t*)nullptr));
+                          nf, ends, part, part64, (const uint32_t*)nullptr));
             GD_TRY(launch(h, "k_scan_down", dim3(nb), dim3(BLOCK), 0, k_scan_down<OpAdd, 4>, (const uint32_t*)ends, ends,
                           nf, false, true, (const uint32_t*)part, nb));
         }
-        HIP_TRY(h, hipMemcpyAsync(h->h_pin, part, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipMemcpyAsync(h->h_pin, part64, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
         GD_TRY(sync(h));
-        uint64_t t = 0;
-        for (uint32_t b = 0; b < nb; ++b) t += ((const uint32_t*)h->h_pin)[b];
+        uint64_t t = 0;                // nb <= 4,096 sums below 2^44 each: no u64 wrap
+        for (uint32_t b = 0; b < nb; ++b) t += ((const unsigned long long*)h->h_pin)[b];
         if (t > 0xFFFFFFFFull) return set_err(h, GD_EINVAL, "fan-out of %llu messages exceeds 2^32 - 1",
                                               (unsigned long long)t);
         *total = t;
@@ -231,24 +236,25 @@ int fan_count_post(gd_handle* h, const uint32_t* row_off, uint32_t n_nodes, cons
     const bool wide = nb4 > 2048;
     const uint32_t nb = wide ? nb16 : nb4;
     GD_TRY(ensure(h, h->fan[0], (size_t)nf_max * 4));
-    GD_TRY(ensure(h, h->fan[1], (size_t)nb * 4));
-    GD_TRY(pinned_scratch(h, ((size_t)nb + 1) * 4));
+    GD_TRY(ensure(h, h->fan[1], fan_part64_off(nb) + (size_t)nb * 8));
+    GD_TRY(pinned_scratch(h, ((size_t)nb + 1) * 8));
     if (!h->fan_ev) HIP_TRY(h, hipEventCreateWithFlags(&h->fan_ev, hipEventDisableTiming));
     uint32_t* ends = (uint32_t*)h->fan[0].p;
     uint32_t* part = (uint32_t*)h->fan[1].p;
+    unsigned long long* part64 = (unsigned long long*)((char*)h->fan[1].p + fan_part64_off(nb));
     if (wide) {
         GD_TRY(launch(h, "k_fan_degree", dim3(nb), dim3(BLOCK), 0, k_fan_degree_tiles<16>, row_off, n_nodes, frontier,
-                      nf_max, ends, part, d_nf));
+                      nf_max, ends, part, part64, d_nf));
         GD_TRY(launch(h, "k_scan_down", dim3(nb), dim3(BLOCK), 0, k_scan_down<OpAdd, 16>, (const uint32_t*)ends, ends,
                       nf_max, false, true, (const uint32_t*)part, nb));
     } else {
         GD_TRY(launch(h, "k_fan_degree", dim3(nb), dim3(BLOCK), 0, k_fan_degree_tiles<4>, row_off, n_nodes, frontier,
-                      nf_max, ends, part, d_nf));
+                      nf_max, ends, part, part64, d_nf));
         GD_TRY(launch(h, "k_scan_down", dim3(nb), dim3(BLOCK), 0, k_scan_down<OpAdd, 4>, (const uint32_t*)ends, ends,
                       nf_max, false, true, (const uint32_t*)part, nb));
     }
-    uint32_t* pin = (uint32_t*)h->h_pin;
-    HIP_TRY(h, hipMemcpyAsync(pin, part, (size_t)nb * 4, hipMemcpyDeviceToHost, h->stream));
+    unsigned long long* pin = (unsigned long long*)h->h_pin;   // nb u64 tile sums, then the length
+    HIP_TRY(h, hipMemcpyAsync(pin, part64, (size_t)nb * 8, hipMemcpyDeviceToHost, h->stream));
     if (d_nf) HIP_TRY(h, hipMemcpyAsync(pin + nb, d_nf, 4, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipEventRecord(h->fan_ev, h->stream));
     *nb_out = nb;
@@ -259,12 +265,12 @@ int fan_count_post(gd_handle* h, const uint32_t* row_off, uint32_t n_nodes, cons
 // length and the hop's u64 total.
 int fan_count_wait(gd_handle* h, uint32_t nb, const uint32_t* d_nf, uint32_t nf_max, uint32_t* nf, uint64_t* total) {
     HIP_TRY(h, hipEventSynchronize(h->fan_ev));
-    const uint32_t* pin = (const uint32_t*)h->h_pin;
+    const unsigned long long* pin = (const unsigned long long*)h->h_pin;
     uint64_t t = 0;
     for (uint32_t b = 0; b < nb; ++b) t += pin[b];
     if (t > 0xFFFFFFFFull)
         return set_err(h, GD_EINVAL, "fan-out of %llu messages exceeds 2^32 - 1", (unsigned long long)t);
-    *nf = d_nf ? pin[nb] : nf_max;
+    *nf = d_nf ? *(const uint32_t*)(pin + nb) : nf_max;
     *total = t;
     return GD_OK;
 }

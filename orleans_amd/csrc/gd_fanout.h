@@ -59,18 +59,22 @@ static __global__ void __launch_bounds__(BLOCK) k_fan_degree(const uint32_t* __r
 // The same as the first half of a scan: block b covers the scan tile b of k_scan_down<OpAdd, IPT>
 // (entries b * IPT * BLOCK ..), writes the degrees (coalesced: entry b * IPT * BLOCK + k * BLOCK + t
 // for thread t) and the tile's sum to part[b], so the inclusive scan of ends is the down-sweep
-// alone; the host adds the partials up for the u64 total.
+// alone.  The sum is taken in 64 bits: part[b] is its low word (all k_scan_down folds; the prefixes
+// of a hop the host refuses may wrap), part64[b] the whole of it, which the host adds up for the u64
+// total -- 1,024 entries naming a publisher of 2^22 followers sum to 2^32, a u32 partial of 0.
 template <int IPT>
 // d_nf (optional): the frontier's length on the device (<= n_front, the grid's bound), as
 // k_frontier_compact left it -- the in-library cascade sizes a hop without reading it back first.
 static __global__ void __launch_bounds__(BLOCK) k_fan_degree_tiles(const uint32_t* __restrict__ row_off, uint32_t n_nodes,
                                                             const uint32_t* __restrict__ frontier, uint32_t n_front,
                                                             uint32_t* __restrict__ ends, uint32_t* __restrict__ part,
+                                                            unsigned long long* __restrict__ part64,
                                                             const uint32_t* __restrict__ d_nf) {
-    __shared__ uint32_t s_wsum[BLOCK / WAVE];
+    __shared__ unsigned long long s_wsum[BLOCK / WAVE];
     if (d_nf) n_front = min(n_front, *d_nf);
     const uint32_t i0 = blockIdx.x * (BLOCK * IPT) + threadIdx.x;
-    uint32_t u[IPT], v = 0;
+    uint32_t u[IPT];
+    unsigned long long v = 0;
 #pragma unroll
     for (int k = 0; k < IPT; ++k) {
         const uint32_t i = i0 + k * BLOCK;
@@ -83,8 +87,17 @@ static __global__ void __launch_bounds__(BLOCK) k_fan_degree_tiles(const uint32_
         if (i < n_front) ends[i] = d;
         v += d;
     }
-    v = block_reduce<OpAdd>(v, s_wsum);
-    if (threadIdx.x == 0) part[blockIdx.x] = v;
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    if ((threadIdx.x & (WAVE - 1)) == 0) s_wsum[threadIdx.x / WAVE] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long s = 0;
+#pragma unroll
+        for (int k = 0; k < BLOCK / WAVE; ++k) s += s_wsum[k];
+        part[blockIdx.x] = (uint32_t)s;
+        part64[blockIdx.x] = s;
+    }
 }
 
 // first i in [lo, hi) with a[i] > p  (hi if none)
