@@ -916,8 +916,9 @@ int gd_receive_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const 
  * <= 65,536, 1 <= n_queues <= 1,024 (SiloMessagingOptions.SiloSenderQueues), else GD_EINVAL; may be
  * called again (the silo table grows); synchronizes the handle.  The batch calls return GD_ESTATE before
  * it (a NULL handle has no configuration: GD_ESTATE too, after the argument checks).
- * Left to C#: the stopped flag (:58-62), QueuedTime, the gateway proxy check (:77), the ShouldDrop test
- * hook, and MessageCenter.SendMessage's IsBlockingApplicationMessages filter (MessageCenter.cs:177-191). */
+ * Left to C#: the stopped flag (:58-62), QueuedTime, the ShouldDrop test hook, and MessageCenter.SendMessage's
+ * IsBlockingApplicationMessages filter (MessageCenter.cs:177-191).  The gateway proxy check (:77) is
+ * gd_gateway_send_queues (the gateway block below); these calls run the rule without it. */
 #define GD_TTL_NONE INT64_MAX           /* TimeToLive has no value */
 #define GD_SEND_QUEUED       0
 #define GD_SEND_LOOPBACK     1
@@ -1443,7 +1444,8 @@ int gd_collect_count_recent(gd_handle* h, const gd_collect_state* st, uint32_t n
  * GD_ESTATE inside a capture.  n <= 2^31; n == 0 is valid.
  *
  * Left to C#: TransactionInfo.Join, the statistics, the callback invocation itself, the actual resend
- * (ResendMessageImpl), TryDeliverToProxy, logging. */
+ * (ResendMessageImpl), logging.  Dispatcher.ReceiveResponse's TryDeliverToProxy (Core/Dispatcher.cs:250) is
+ * gd_gateway_deliver (the gateway block below), run ahead of respond on the same batch. */
 #define GD_CB_NONE            0
 #define GD_CB_FIRE            1
 #define GD_CB_RESEND          2
@@ -1485,6 +1487,165 @@ int gd_callbacks_break_silo_device(gd_handle* h, uint32_t silo, uint32_t cap, in
                                    uint8_t* d_out_kind, uint32_t* d_n_out);
 int gd_callbacks_break_silo(gd_handle* h, uint32_t silo, uint32_t cap, int64_t* out_id, uint32_t* out_handle,
                             uint8_t* out_kind, uint32_t* n_out);
+
+/* ---- gateway: client table, TryDeliverToProxy, reply routes, client ingress ---------------
+ * What a client-facing silo does per message in Messaging/Gateway.cs and GatewayAcceptor.cs that is not socket
+ * code, for a batch: Gateway.clients (ConcurrentDictionary<GrainId, ClientState>, Gateway.cs:265-306) and
+ * ClientsReplyRoutingCache.clientRoutes (:340-383) as two open-addressing tables per handle in device memory,
+ * both keyed by the client's 24-B GrainId, category Client (UniqueKey.Category 4; GrainId.cs:23).  A client
+ * entry holds the host's ClientState handle (u32, never interpreted here), GatewaySenderNumber, the connected
+ * flag (Socket != null), DisconnectedSince (int64 ticks, INT64_MAX while connected: RecordConnection sets
+ * DateTime.MaxValue, :295-299) and PendingToSend.Count (u32).  A route holds the gateway silo index (GD_NO_SILO
+ * allowed: a null SendingSilo) and the tick it was recorded at.  Ticks are DateTime ticks: differences of two of
+ * them do not overflow.  Calls are serialised by the caller, like every table of the handle; a batch gives the
+ * results of its messages taken one by one in array order.  Geo clients (category GeoClient, 7) carry a KeyExt
+ * string in their identity: every call reports them with a status of its own and does not touch them.
+ *
+ * gd_gateway_configure(n_senders, client_drop_timeout, route_expiry, capacity_hint): the first call creates both
+ *   tables (a power of two >= max(capacity_hint, 64) slots each); a later call changes the options and grows the
+ *   tables if the hint asks for more.  1 <= n_senders <= 1,024 (senders.Length); changing it while clients are
+ *   present is GD_EINVAL.  client_drop_timeout = MessagingOptions.ClientDropTimeout, route_expiry = 5 x
+ *   ResponseTimeout (:349), both in ticks, >= 0.  The other calls return GD_ESTATE before it.
+ *   gd_gateway_clear empties both tables and resets the round robin; gd_gateway_count reads the live clients, the
+ *   live routes and the two capacities (each output may be NULL).  A table holds live entries and the tombstones
+ *   of removed ones; when both pass 0.75 of the slots, open (clients) or deliver (routes) rebuilds it on the
+ *   stream, at the same capacity while the live entries fill at most half of it, else at double.
+ * open = RecordOpenedSocket (:117-147), in array order.  An absent id is inserted with handles[i], sender
+ *   (next_round_robin + its rank among the batch's new ids) % n_senders (:136-138), connected, pending 0:
+ *   out_new = 1.  A present id -- in the table, or first seen earlier in the batch -- is a reconnect: it becomes
+ *   connected, DisconnectedSince = INT64_MAX, out_new = 0, out_handle = the stored handle, out_pending = its
+ *   pending count, which becomes 0 (QueueRequest(clientState, null), :132: the drain; the host sends its own
+ *   queue).  next_round_robin advances by the number of new ids.  A key that is not of category Client gets
+ *   out_new = GD_GW_NOT_CLIENT, out_handle 0xFFFFFFFF, out_sender = n_senders, and is not touched.  Each output
+ *   may be NULL.
+ * close = RecordClosedSocket -> RecordDisconnection (:149-169, :286-293).  A present, connected id: connected = 0,
+ *   DisconnectedSince = now, and with pending_left given pending = pending_left[i] (what the host still holds
+ *   after a failed drain); out_found = 1.  A present, disconnected id is untouched (Socket == null returns),
+ *   out_found = 1.  Absent (or not a Client key): out_found = 0.  Which socket is which client's (clientSockets)
+ *   stays in C#.
+ * drop = DropDisconnectedClients (:182-222): every entry with !connected && now - DisconnectedSince >=
+ *   client_drop_timeout (ReadyToDrop, :301-305) is removed and listed in out_id / out_handle / out_pending
+ *   [0 .. *n_out), in no particular order.  *n_out > cap: nothing was changed or listed (host form: GD_EINVAL;
+ *   device form: the caller compares the device word with cap).
+ * routes_expire = DropExpiredEntries (:369-382): removes every route with now - recorded >= route_expiry;
+ *   *n_removed = how many.
+ * lookup: read-only.  Clients: out_handle (0xFFFFFFFF absent), out_sender (n_senders), out_connected (0),
+ *   out_since (0), out_pending (0), out_found; routes: out_route_silo (GD_NO_SILO), out_route_time (0),
+ *   out_route_found.  Each output may be NULL.
+ * deliver = TryDeliverToProxy (:229-250) behind OutboundMessageQueue.cs:65-80, plus what GatewaySender.Process
+ *   (:401-475) then decides.  Per message: target_grain, sending_grain (array NULL: no sender is a client),
+ *   sending_silo (array NULL: GD_NO_SILO), ttl (gd_send_queues' meaning; NULL: none expire); scalar now.
+ *   Statuses, in the reference's order:
+ *     GD_GW_EXPIRED      ttl != GD_TTL_NONE && ttl <= 0 (OutboundMessageQueue.cs:65 runs before the proxy check)
+ *     GD_GW_GEO_CLIENT   the target is a geo client: left to C#
+ *     GD_GW_NOT_PROXIED  the target is not a Client or not in the client table: TryDeliverToProxy returns false
+ *     GD_GW_SEND         the client is present and connected (Process sends on its socket)
+ *     GD_GW_PENDING      present and disconnected: Process enqueues on PendingToSend (:424-429): pending += 1
+ *   Process's "unrecognised client" branch (:411-416) cannot occur: lookup and processing are one step here.
+ *   For every message that found its client and whose sending_grain is of category Client, the route table gets
+ *   sending_grain -> (sending_silo, now) (RecordClientRoute = AddOrUpdate, :352-356): the last such message of
+ *   a grain in the batch stands.  A geo-client sender is not recorded.
+ *   out_handle: the ClientState handle (0xFFFFFFFF unless SEND or PENDING); out_sender: the client's sender number
+ *   (n_senders for every other status).  perm[n] + offsets[n_senders + 2] (optional, both or neither): the batch's
+ *   indices grouped by sender, each sender's in batch order (AsynchQueueAgent is a FIFO); everything not SEND or
+ *   PENDING in the trailing bucket n_senders; offsets[n_senders + 1] = n.  n == 0 fills offsets with zeros.
+ * send_queues = the send stage with the proxy check in its place (OutboundMessageQueue.cs:54-131): gd_send_queues'
+ *   rule (gd_send_configure first) with one status added, GD_SEND_PROXIED, decided after HELD and EXPIRED and
+ *   before NO_SILO (:77).  A proxied message gets deliver's out_handle and side effects; out_queue = n_queues + 4 +
+ *   its sender number.  Buckets: gd_send_queues' n_queues + 4 unchanged, then one per gateway sender:
+ *   offsets[n_queues + n_senders + 5], the last entry n.  The result equals gd_gateway_deliver followed by
+ *   gd_send_queues on the not-proxied rest.
+ * ingress = GatewayAcceptor.HandleMessage (GatewayAcceptor.cs:88-141) for a batch received from clients; read-only
+ *   on the tables.  Per message: target_grain, sending_grain (NULL: no sender is a client), direction (gd_receive's
+ *   byte, 1 = Response; NULL: all Requests), ttl (NULL: none expire); scalar overloaded (overloadDetector.Overloaded).
+ *     GD_GWIN_EXPIRED        (:91)
+ *     GD_GWIN_TOO_BUSY       overloaded (:106-114): the rejection and its TryDeliverToProxy are the caller's
+ *     GD_GWIN_GEO_CLIENT     sender and target both IsClient, a Response, and the target a geo client: TryToReroute's
+ *                            lookup is left to C# (categories compared only; both kinds count as IsClient)
+ *     GD_GWIN_DIRECT         sender and target both IsClient, a Response, and the route table holds the target with
+ *                            a silo other than GD_NO_SILO (Gateway.cs:171-180): out_silo = it, the caller calls
+ *                            SendMessage (:138-139).  A route found with GD_NO_SILO is a null gateway: it reroutes.
+ *     GD_GWIN_SYSTEM_TARGET  rerouted and the target a system target (:126-130): out_silo = gd_config.my_silo
+ *     GD_GWIN_REROUTE        address cleared (:122-124): the message goes to gd_route*
+ *   out_silo is GD_NO_SILO unless DIRECT or SYSTEM_TARGET.  route_idx[n] + n_route (optional, both or neither): the
+ *   REROUTE messages in array order; route_keys[n] (optional, with them): their 24-B target keys compacted in that
+ *   order, for gd_route_device with no host step.
+ *
+ * The *_device forms take device pointers (n_out / n_removed / n_route device words) and only enqueue on the
+ * handle's stream, except that an open or a deliver whose room cannot be told from the host's bound reads the
+ * counters back (GD_ESTATE inside a hipGraph capture; the bound counts one new entry a message); they run 12 gated
+ * claim passes, and a batch of new ids that did not settle in them is reported as GD_ETIMEOUT by the next
+ * synchronising gd_gateway_* call.  The host forms are synchronous and return GD_ESTATE inside a capture.
+ * n <= 2^31; n == 0 is valid.
+ *
+ * Left to C#: the sockets and clientSockets, the PendingToSend queues themselves and their batches, rewriting
+ * TargetSilo = null / SendingSilo = gatewayAddress in the frame (:246-247; gd_encode_frames* takes the caller's
+ * fields), HasMultiClusterNetwork's sender translation (GatewayAcceptor.cs:100-103), clientRegistrar, statistics,
+ * logging. */
+#define GD_GW_NOT_PROXIED  0
+#define GD_GW_SEND         1
+#define GD_GW_PENDING      2
+#define GD_GW_EXPIRED      3
+#define GD_GW_GEO_CLIENT   4
+#define GD_GW_NOT_CLIENT   0xFF              /* open's out_new */
+#define GD_GW_MAX_SENDERS  1024u
+#define GD_SEND_PROXIED    7                 /* gd_gateway_send_queues' added send status */
+#define GD_GWIN_REROUTE        0
+#define GD_GWIN_DIRECT         1
+#define GD_GWIN_SYSTEM_TARGET  2
+#define GD_GWIN_EXPIRED        3
+#define GD_GWIN_TOO_BUSY       4
+#define GD_GWIN_GEO_CLIENT     5
+int gd_gateway_configure(gd_handle* h, uint32_t n_senders, int64_t client_drop_timeout, int64_t route_expiry,
+                         uint64_t capacity_hint);
+int gd_gateway_clear(gd_handle* h);
+int gd_gateway_count(gd_handle* h, uint64_t* out_clients, uint64_t* out_routes, uint64_t* out_client_capacity,
+                     uint64_t* out_route_capacity);
+int gd_gateway_open_device(gd_handle* h, const gd_key* d_ids, const uint32_t* d_handles, uint32_t n,
+                           uint32_t* d_out_handle, uint32_t* d_out_sender, uint8_t* d_out_new, uint32_t* d_out_pending);
+int gd_gateway_open(gd_handle* h, const gd_key* ids, const uint32_t* handles, uint32_t n, uint32_t* out_handle,
+                    uint32_t* out_sender, uint8_t* out_new, uint32_t* out_pending);
+int gd_gateway_close_device(gd_handle* h, const gd_key* d_ids, const uint32_t* d_pending_left, uint32_t n, int64_t now,
+                            uint8_t* d_out_found);
+int gd_gateway_close(gd_handle* h, const gd_key* ids, const uint32_t* pending_left, uint32_t n, int64_t now,
+                     uint8_t* out_found);
+int gd_gateway_drop_device(gd_handle* h, int64_t now, uint32_t cap, gd_key* d_out_id, uint32_t* d_out_handle,
+                           uint32_t* d_out_pending, uint32_t* d_n_out);
+int gd_gateway_drop(gd_handle* h, int64_t now, uint32_t cap, gd_key* out_id, uint32_t* out_handle,
+                    uint32_t* out_pending, uint32_t* n_out);
+int gd_gateway_routes_expire_device(gd_handle* h, int64_t now, uint32_t* d_n_removed);
+int gd_gateway_routes_expire(gd_handle* h, int64_t now, uint32_t* n_removed);
+int gd_gateway_lookup_device(gd_handle* h, const gd_key* d_ids, uint32_t n, uint32_t* d_out_handle,
+                             uint32_t* d_out_sender, uint8_t* d_out_connected, int64_t* d_out_since,
+                             uint32_t* d_out_pending, uint8_t* d_out_found, uint32_t* d_out_route_silo,
+                             int64_t* d_out_route_time, uint8_t* d_out_route_found);
+int gd_gateway_lookup(gd_handle* h, const gd_key* ids, uint32_t n, uint32_t* out_handle, uint32_t* out_sender,
+                      uint8_t* out_connected, int64_t* out_since, uint32_t* out_pending, uint8_t* out_found,
+                      uint32_t* out_route_silo, int64_t* out_route_time, uint8_t* out_route_found);
+int gd_gateway_deliver_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_sending_grain,
+                              const uint32_t* d_sending_silo, const int64_t* d_ttl, uint32_t n, int64_t now,
+                              uint8_t* d_out_status, uint32_t* d_out_handle, uint32_t* d_out_sender, uint32_t* d_perm,
+                              uint32_t* d_offsets);
+int gd_gateway_deliver(gd_handle* h, const gd_key* target_grain, const gd_key* sending_grain,
+                       const uint32_t* sending_silo, const int64_t* ttl, uint32_t n, int64_t now, uint8_t* out_status,
+                       uint32_t* out_handle, uint32_t* out_sender, uint32_t* out_perm, uint32_t* out_offsets);
+int gd_gateway_send_queues_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_sending_grain,
+                                  const uint32_t* d_sending_silo, const uint32_t* d_silo,
+                                  const uint8_t* d_route_status, const uint8_t* d_category, const int64_t* d_ttl,
+                                  uint32_t n, int64_t now, uint8_t* d_send_status, uint32_t* d_queue,
+                                  uint32_t* d_out_handle, uint32_t* d_perm, uint32_t* d_offsets);
+int gd_gateway_send_queues(gd_handle* h, const gd_key* target_grain, const gd_key* sending_grain,
+                           const uint32_t* sending_silo, const uint32_t* silo, const uint8_t* route_status,
+                           const uint8_t* category, const int64_t* ttl, uint32_t n, int64_t now,
+                           uint8_t* out_send_status, uint32_t* out_queue, uint32_t* out_handle, uint32_t* out_perm,
+                           uint32_t* out_offsets);
+int gd_gateway_ingress_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_sending_grain,
+                              const uint8_t* d_direction, const int64_t* d_ttl, uint32_t n, int overloaded,
+                              uint8_t* d_out_status, uint32_t* d_out_silo, uint32_t* d_route_idx, uint32_t* d_n_route,
+                              gd_key* d_route_keys);
+int gd_gateway_ingress(gd_handle* h, const gd_key* target_grain, const gd_key* sending_grain, const uint8_t* direction,
+                       const int64_t* ttl, uint32_t n, int overloaded, uint8_t* out_status, uint32_t* out_silo,
+                       uint32_t* route_idx, uint32_t* n_route, gd_key* route_keys);
 
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */

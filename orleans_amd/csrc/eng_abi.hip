@@ -116,6 +116,10 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->pump_scr) free_buf(b);
     for (DevBuf* b : {&h->cb_tab, &h->cb_dl, &h->cb_ctr, &h->cb_last}) free_buf(*b);
     for (DevBuf& b : h->cb_scr) free_buf(b);
+    for (int t = 0; t < 2; ++t)
+        for (DevBuf* b : {&h->gw_slots[t], &h->gw_side[t], &h->gw_ctr[t], &h->gw_last[t]}) free_buf(*b);
+    free_buf(h->gw_state);
+    for (DevBuf& b : h->gw_scr) free_buf(b);
     for (DevBuf& b : h->enc_tab) free_buf(b);
     for (DevBuf& b : h->enc_scr) free_buf(b);
     for (DevBuf& b : h->col_scr) free_buf(b);

@@ -172,6 +172,16 @@ struct gd_handle {
     DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller
                                       // wants none; quantum keys; their bucket offsets
 
+    // gateway (gd_gateway.h, eng_gateway.hip): [0] the client table, [1] the reply routes; each the 32-B slots,
+    // the values beside them (GwClient / the route's time), DevCounters + stripes, two election words a slot
+    DevBuf gw_slots[2], gw_side[2], gw_ctr[2], gw_last[2];
+    unsigned long long gw_cap[2] = {0, 0};
+    uint64_t gw_used_ub[2] = {0, 0};  // live + tombstones at most: the last read-back plus every possible add since
+    DevBuf gw_state;                  // GwState: next_round_robin, the gated passes' deferred counts
+    uint32_t gw_nsenders = 0;         // 0: not configured (gd_gateway_configure)
+    int64_t gw_drop_timeout = 0, gw_route_expiry = 0;
+    DevBuf gw_scr[6];                 // slot_of, is_new, scan flags, bucket counts, statuses / bucket ids unasked for
+
     // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
     // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads

@@ -89,6 +89,11 @@ EXPORTED_SYMBOLS = [
     "gd_callbacks_add", "gd_callbacks_set_target_device", "gd_callbacks_set_target", "gd_callbacks_lookup_device",
     "gd_callbacks_lookup", "gd_callbacks_respond_device", "gd_callbacks_respond", "gd_callbacks_expire_device",
     "gd_callbacks_expire", "gd_callbacks_break_silo_device", "gd_callbacks_break_silo",
+    "gd_gateway_configure", "gd_gateway_clear", "gd_gateway_count", "gd_gateway_open_device", "gd_gateway_open",
+    "gd_gateway_close_device", "gd_gateway_close", "gd_gateway_drop_device", "gd_gateway_drop",
+    "gd_gateway_routes_expire_device", "gd_gateway_routes_expire", "gd_gateway_lookup_device", "gd_gateway_lookup",
+    "gd_gateway_deliver_device", "gd_gateway_deliver", "gd_gateway_send_queues_device", "gd_gateway_send_queues",
+    "gd_gateway_ingress_device", "gd_gateway_ingress",
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
@@ -350,6 +355,25 @@ def _load() -> C.CDLL:
         "gd_callbacks_expire": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
         "gd_callbacks_break_silo_device": (C.c_int, [P, U32, U32, P, P, P, P]),
         "gd_callbacks_break_silo": (C.c_int, [P, U32, U32, P, P, P, P]),
+        "gd_gateway_configure": (C.c_int, [P, U32, C.c_int64, C.c_int64, U64]),
+        "gd_gateway_clear": (C.c_int, [P]),
+        "gd_gateway_count": (C.c_int, [P] + [C.POINTER(U64)] * 4),
+        "gd_gateway_open_device": (C.c_int, [P, P, P, U32, P, P, P, P]),
+        "gd_gateway_open": (C.c_int, [P, P, P, U32, P, P, P, P]),
+        "gd_gateway_close_device": (C.c_int, [P, P, P, U32, C.c_int64, P]),
+        "gd_gateway_close": (C.c_int, [P, P, P, U32, C.c_int64, P]),
+        "gd_gateway_drop_device": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
+        "gd_gateway_drop": (C.c_int, [P, C.c_int64, U32, P, P, P, P]),
+        "gd_gateway_routes_expire_device": (C.c_int, [P, C.c_int64, P]),
+        "gd_gateway_routes_expire": (C.c_int, [P, C.c_int64, P]),
+        "gd_gateway_lookup_device": (C.c_int, [P, P, U32] + [P] * 9),
+        "gd_gateway_lookup": (C.c_int, [P, P, U32] + [P] * 9),
+        "gd_gateway_deliver_device": (C.c_int, [P, P, P, P, P, U32, C.c_int64, P, P, P, P, P]),
+        "gd_gateway_deliver": (C.c_int, [P, P, P, P, P, U32, C.c_int64, P, P, P, P, P]),
+        "gd_gateway_send_queues_device": (C.c_int, [P] + [P] * 7 + [U32, C.c_int64] + [P] * 5),
+        "gd_gateway_send_queues": (C.c_int, [P] + [P] * 7 + [U32, C.c_int64] + [P] * 5),
+        "gd_gateway_ingress_device": (C.c_int, [P, P, P, P, P, U32, C.c_int, P, P, P, P, P]),
+        "gd_gateway_ingress": (C.c_int, [P, P, P, P, P, U32, C.c_int, P, P, P, P, P]),
         "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
         "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
@@ -1293,6 +1317,161 @@ class GrainDispatch:
         V = lambda x: C.c_void_p(x or 0)
         self._c(lib.gd_callbacks_break_silo_device(self.h, silo, cap, V(d_out_id), V(d_out_handle), V(d_out_kind),
                                                    V(d_n_out)))
+
+    # -- gateway (Messaging/Gateway.cs, GatewayAcceptor.cs) ------------------------------------------
+    def gateway_configure(self, n_senders: int, client_drop_timeout: int, route_expiry: int, capacity_hint: int = 0):
+        self._c(lib.gd_gateway_configure(self.h, n_senders, client_drop_timeout, route_expiry, capacity_hint))
+        self.gateway_n_senders = n_senders
+
+    def gateway_clear(self):
+        self._c(lib.gd_gateway_clear(self.h))
+
+    def gateway_count(self) -> Tuple[int, int, int, int]:
+        """gd_gateway_count: (live clients, live routes, client slots, route slots)."""
+        v = [C.c_uint64(0) for _ in range(4)]
+        self._c(lib.gd_gateway_count(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def gateway_open(self, ids, handles):
+        """gd_gateway_open: (handle u32, sender u32, new u8, pending u32)."""
+        k, hd = keys_array(ids), np.ascontiguousarray(np.asarray(handles, dtype=np.uint32))
+        n = len(k)
+        oh, os_, on, op = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        self._c(lib.gd_gateway_open(self.h, _ptr(k), _ptr(hd), n, _ptr(oh), _ptr(os_), _ptr(on), _ptr(op)))
+        return oh, os_, on, op
+
+    def gateway_close(self, ids, now: int, pending_left=None) -> np.ndarray:
+        """gd_gateway_close: found u8[n]."""
+        k, pl = keys_array(ids), self._opt(pending_left, np.uint32)
+        out = np.zeros(len(k), np.uint8)
+        self._c(lib.gd_gateway_close(self.h, _ptr(k), None if pl is None else _ptr(pl), len(k), now, _ptr(out)))
+        return out
+
+    def gateway_drop(self, now: int, cap: int):
+        """gd_gateway_drop: (id u64[k, 3], handle u32, pending u32) of the dropped clients, in no particular order."""
+        ids, hd, pd = np.zeros((max(cap, 1), 3), np.uint64), np.zeros(max(cap, 1), np.uint32), np.zeros(max(cap, 1), np.uint32)
+        n = np.zeros(1, np.uint32)
+        self._c(lib.gd_gateway_drop(self.h, now, cap, _ptr(ids), _ptr(hd), _ptr(pd), _ptr(n)))
+        k = int(n[0])
+        return ids[:k].copy(), hd[:k].copy(), pd[:k].copy()
+
+    def gateway_routes_expire(self, now: int) -> int:
+        n = np.zeros(1, np.uint32)
+        self._c(lib.gd_gateway_routes_expire(self.h, now, _ptr(n)))
+        return int(n[0])
+
+    def gateway_lookup(self, ids):
+        """gd_gateway_lookup: (handle u32, sender u32, connected u8, since i64, pending u32, found u8, route_silo u32,
+        route_time i64, route_found u8)."""
+        k = keys_array(ids)
+        n = len(k)
+        out = [np.zeros(n, t) for t in (np.uint32, np.uint32, np.uint8, np.int64, np.uint32, np.uint8, np.uint32,
+                                        np.int64, np.uint8)]
+        self._c(lib.gd_gateway_lookup(self.h, _ptr(k), n, *[_ptr(a) for a in out]))
+        return tuple(out)
+
+    def gateway_deliver(self, target_grain, sending_grain, sending_silo, now: int, ttl=None, bucket: bool = True):
+        """gd_gateway_deliver: (status u8, handle u32, sender u32[, perm, offsets[n_senders + 2]])."""
+        t = keys_array(target_grain)
+        n = len(t)
+        s = None if sending_grain is None else keys_array(sending_grain)
+        ss, tl = self._opt(sending_silo, np.uint32), self._opt(ttl, np.int64)
+        p = lambda a: None if a is None else _ptr(a)
+        st, hd, sd = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        perm = np.zeros(n, np.uint32) if bucket else None
+        off = np.zeros(self.gateway_n_senders + 2, np.uint32) if bucket else None
+        self._c(lib.gd_gateway_deliver(self.h, _ptr(t), p(s), p(ss), p(tl), n, now, _ptr(st), _ptr(hd), _ptr(sd), p(perm),
+                                       p(off)))
+        return (st, hd, sd, perm, off) if bucket else (st, hd, sd)
+
+    def gateway_send_queues(self, target_grain, sending_grain, sending_silo, silo, now: int, route_status=None,
+                            category=None, ttl=None, bucket: bool = True):
+        """gd_gateway_send_queues: (send_status u8, queue u32, handle u32[, perm, offsets[n_queues + n_senders + 5]])."""
+        t = keys_array(target_grain)
+        n = len(t)
+        s = None if sending_grain is None else keys_array(sending_grain)
+        ss, sl = self._opt(sending_silo, np.uint32), np.ascontiguousarray(np.asarray(silo, dtype=np.uint32))
+        rs, cat, tl = self._opt(route_status, np.uint8), self._opt(category, np.uint8), self._opt(ttl, np.int64)
+        p = lambda a: None if a is None else _ptr(a)
+        st, q, hd = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        perm = np.zeros(n, np.uint32) if bucket else None
+        off = np.zeros(self.send_n_queues + self.gateway_n_senders + 5, np.uint32) if bucket else None
+        self._c(lib.gd_gateway_send_queues(self.h, _ptr(t), p(s), p(ss), _ptr(sl), p(rs), p(cat), p(tl), n, now, _ptr(st),
+                                           _ptr(q), _ptr(hd), p(perm), p(off)))
+        return (st, q, hd, perm, off) if bucket else (st, q, hd)
+
+    def gateway_ingress(self, target_grain, sending_grain, direction=None, ttl=None, overloaded: bool = False,
+                        routes: bool = True):
+        """gd_gateway_ingress: (status u8, silo u32[, route_idx u32[n_route], route_keys u64[n_route, 3]])."""
+        t = keys_array(target_grain)
+        n = len(t)
+        s = None if sending_grain is None else keys_array(sending_grain)
+        d, tl = self._opt(direction, np.uint8), self._opt(ttl, np.int64)
+        p = lambda a: None if a is None else _ptr(a)
+        st, sl = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        ri = np.zeros(max(n, 1), np.uint32) if routes else None
+        nr = np.zeros(1, np.uint32) if routes else None
+        rk = np.zeros((max(n, 1), 3), np.uint64) if routes else None
+        self._c(lib.gd_gateway_ingress(self.h, _ptr(t), p(s), p(d), p(tl), n, int(overloaded), _ptr(st), _ptr(sl), p(ri),
+                                       p(nr), p(rk)))
+        return (st, sl, ri[:int(nr[0])].copy(), rk[:int(nr[0])].copy()) if routes else (st, sl)
+
+    def gateway_open_device(self, d_ids: int, d_handles: int, n: int, d_out_handle: Optional[int] = None,
+                            d_out_sender: Optional[int] = None, d_out_new: Optional[int] = None,
+                            d_out_pending: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_open_device(self.h, V(d_ids), V(d_handles), n, V(d_out_handle), V(d_out_sender),
+                                           V(d_out_new), V(d_out_pending)))
+
+    def gateway_close_device(self, d_ids: int, d_pending_left: Optional[int], n: int, now: int,
+                             d_out_found: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_close_device(self.h, V(d_ids), V(d_pending_left), n, now, V(d_out_found)))
+
+    def gateway_drop_device(self, now: int, cap: int, d_out_id: int, d_out_handle: int, d_out_pending: int, d_n_out: int):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_drop_device(self.h, now, cap, V(d_out_id), V(d_out_handle), V(d_out_pending), V(d_n_out)))
+
+    def gateway_routes_expire_device(self, now: int, d_n_removed: int):
+        self._c(lib.gd_gateway_routes_expire_device(self.h, now, C.c_void_p(d_n_removed or 0)))
+
+    def gateway_lookup_device(self, d_ids: int, n: int, d_out_handle: Optional[int] = None,
+                              d_out_sender: Optional[int] = None, d_out_connected: Optional[int] = None,
+                              d_out_since: Optional[int] = None, d_out_pending: Optional[int] = None,
+                              d_out_found: Optional[int] = None, d_out_route_silo: Optional[int] = None,
+                              d_out_route_time: Optional[int] = None, d_out_route_found: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_lookup_device(self.h, V(d_ids), n, V(d_out_handle), V(d_out_sender), V(d_out_connected),
+                                             V(d_out_since), V(d_out_pending), V(d_out_found), V(d_out_route_silo),
+                                             V(d_out_route_time), V(d_out_route_found)))
+
+    def gateway_deliver_device(self, d_target_grain: int, d_sending_grain: Optional[int], d_sending_silo: Optional[int],
+                               d_ttl: Optional[int], n: int, now: int, d_out_status: int,
+                               d_out_handle: Optional[int] = None, d_out_sender: Optional[int] = None,
+                               d_perm: Optional[int] = None, d_offsets: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_deliver_device(self.h, V(d_target_grain), V(d_sending_grain), V(d_sending_silo), V(d_ttl), n,
+                                              now, V(d_out_status), V(d_out_handle), V(d_out_sender), V(d_perm),
+                                              V(d_offsets)))
+
+    def gateway_send_queues_device(self, d_target_grain: int, d_sending_grain: Optional[int],
+                                   d_sending_silo: Optional[int], d_silo: int, d_route_status: Optional[int],
+                                   d_category: Optional[int], d_ttl: Optional[int], n: int, now: int, d_send_status: int,
+                                   d_queue: Optional[int] = None, d_out_handle: Optional[int] = None,
+                                   d_perm: Optional[int] = None, d_offsets: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_send_queues_device(self.h, V(d_target_grain), V(d_sending_grain), V(d_sending_silo),
+                                                  V(d_silo), V(d_route_status), V(d_category), V(d_ttl), n, now,
+                                                  V(d_send_status), V(d_queue), V(d_out_handle), V(d_perm), V(d_offsets)))
+
+    def gateway_ingress_device(self, d_target_grain: int, d_sending_grain: Optional[int], d_direction: Optional[int],
+                               d_ttl: Optional[int], n: int, overloaded: bool, d_out_status: int,
+                               d_out_silo: Optional[int] = None, d_route_idx: Optional[int] = None,
+                               d_n_route: Optional[int] = None, d_route_keys: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_gateway_ingress_device(self.h, V(d_target_grain), V(d_sending_grain), V(d_direction), V(d_ttl), n,
+                                              int(overloaded), V(d_out_status), V(d_out_silo), V(d_route_idx),
+                                              V(d_n_route), V(d_route_keys)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
