@@ -712,6 +712,123 @@ int gd_cache_entries_ext(gd_handle* h, gd_key* keys, gd_val* vals, int32_t* vers
                          int32_t* ext_len, uint64_t* ext_off, uint8_t* ext_bytes, uint64_t capacity,
                          uint64_t bytes_capacity, uint64_t* out_n, uint64_t* out_bytes);
 
+/* ---- the directory cache's maintainer -----------------------------------------
+ * What makes the cache adaptive: per entry NumAccesses, LastRefreshed and ExpirationTimer
+ * (AdaptiveGrainDirectoryCache.cs:15-35), and AdaptiveDirectoryCacheMaintainer.Run
+ * (AdaptiveDirectoryCacheMaintainer.cs:42-131) over them -- the expiry scan, the per-owner request
+ * lists (SendBatchCacheRefreshRequests :133-153, BuildGrainAndETagList :202-224), the owner's
+ * LookUpMany (RemoteGrainDirectory.cs:65-96) and the response pass (ProcessCacheRefreshResponse
+ * :155-193).  Created (:13) is written by the reference and never read on this path: it is not
+ * stored.  Times are DateTime.Ticks passed in; one `now` stands for every DateTime.UtcNow a call
+ * would read.
+ *
+ * The cache clock (gd_cache_clock_set; scan and apply set it to their `now` first) is the UtcNow of
+ * the add path: every entry gd_cache_add* creates -- a replaced key's too, AddOrUpdate builds a new
+ * entry (:74-80) -- gets LastRefreshed = clock, ExpirationTimer = initial, NumAccesses = 0.  Every
+ * LookUp hit (gd_cache_lookup* and every LocalLookup route form) is one NumAccesses++ on its entry
+ * (:106), duplicates in a batch counted each.
+ *
+ * gd_cache_maintain_configure stores the constructor's parameters (:63-70); before it they are 30 s,
+ * 240 s and 2.0 (GrainDirectoryOptions.cs:31-55).  GD_EINVAL: no cache configured, a negative tick
+ * count, growth not finite or <= 0, (double)max(initial, max) * growth >= 2^62 (the checked overflow
+ * of StandardExtensions.Multiply, refused up front). */
+int gd_cache_maintain_configure(gd_handle* h, int64_t initial_ticks, int64_t max_ticks, double growth, int64_t now);
+int gd_cache_clock_set(gd_handle* h, int64_t now);
+/* LastRefreshed, ExpirationTimer and NumAccesses of every entry in the slot order of gd_cache_entries
+ * (the two dumps zip together); refreshed NULL = size query. */
+int gd_cache_entries_age(gd_handle* h, int64_t* refreshed, int64_t* timer, int32_t* num_accesses, uint64_t capacity,
+                         uint64_t* out_n);
+
+/* Run's loop at `now`.  The reference enumerates a ConcurrentDictionary, whose order is unspecified;
+ * here the enumeration order is ascending cache slot, the order of gd_cache_entries.  Per live entry,
+ * owner = CalculateTargetSilo under the installed ring (a KeyExt entry by its KeyExt hash):
+ *   GD_CM_SELF_OWNED  local_silo[owner] != 0: removed (:79-86)
+ *   GD_CM_FRESH       now < LastRefreshed + ExpirationTimer: nothing (:95-99; IsExpired is >=)
+ *   GD_CM_DROPPED     expired and NumAccesses == 0: removed (:100-105)
+ *   GD_CM_REFRESH     expired and accessed: NumAccesses = 0, appended to its owner's list (:106-117)
+ * The lists: owners in order of first appearance in the enumeration, one owner's candidates in
+ * enumeration order; candidate j of that grouped order takes generation next_generation + j + 1
+ * (BuildGrainAndETagList's cache.Get is LRU.TryGetValue, LRU.cs:124-163; NumAccesses and the
+ * statistics are not touched).  out_counts[5]: entries seen, then the four classes (cnt1..cnt4 of :63
+ * are [1], [2], [3], [4]).
+ *
+ * The scan changes the cache, so it runs once and holds its lists in library buffers until the next
+ * scan on the handle: gd_cache_scan reports their sizes (the size query), gd_cache_scan_fetch copies
+ * them out -- owner[n_owners], offsets[n_owners + 1], and per candidate keys, etags, slots, ext_len
+ * (GD_KEYEXT_NULL for a three-word key) and ext_off into ext_bytes, as gd_cache_entries_ext.  Any
+ * output of the fetch may be NULL.  gd_cache_scan_device gives the same lists as device pointers. */
+#define GD_CM_SEEN       0
+#define GD_CM_SELF_OWNED 1
+#define GD_CM_FRESH      2
+#define GD_CM_DROPPED    3
+#define GD_CM_REFRESH    4
+typedef struct gd_cache_scan_result {
+    uint64_t counts[5];
+    uint32_t n_owners, n;          /* request lists, candidates                                    */
+    uint64_t ext_bytes_len;
+    const uint32_t* owner;         /* device: [n_owners] silo index                                */
+    const uint32_t* offsets;       /* device: [n_owners + 1]                                       */
+    const gd_key* keys;            /* device: [n]                                                  */
+    const int32_t* etags;          /* device: [n]                                                  */
+    const uint32_t* slots;         /* device: [n] cache slot                                       */
+    const int32_t* ext_len;        /* device: [n]                                                  */
+    const uint32_t* ext_off;       /* device: [n] byte offset in ext_bytes                         */
+    const uint8_t* ext_bytes;      /* device: [ext_bytes_len]                                      */
+} gd_cache_scan_result;
+int gd_cache_scan_device(gd_handle* h, int64_t now, gd_cache_scan_result* out);
+int gd_cache_scan(gd_handle* h, int64_t now, uint64_t* out_counts, uint32_t* out_n_owners, uint32_t* out_n,
+                  uint64_t* out_bytes);
+int gd_cache_scan_fetch(gd_handle* h, uint32_t* owner, uint32_t* offsets, gd_key* keys, int32_t* etags,
+                        uint32_t* slots, int32_t* ext_len, uint64_t* ext_off, uint8_t* ext_bytes,
+                        uint32_t owner_capacity, uint32_t capacity, uint64_t bytes_capacity);
+
+/* The owner side, LookUpMany per item (items are independent).  cur = GetGrainETag
+ * (GrainDirectoryPartition.cs:479-491): the entry's VersionTag, -1 without one.
+ *   GD_LM_SAME     cur == etag and cur != -1: out_tags = cur, no value
+ *   GD_LM_ABSENT   cur == -1: out_tags = -1
+ *   GD_LM_UPDATED  otherwise: out_tags = the VersionTag, out_vals as gd_dir_lookup_tagged gives it,
+ *                  {GD_NO_ACTIVATION, GD_NO_SILO} for an entry whose silo fails IsValidSilo (the filtered
+ *                  list is empty, not null, and the requester caches the empty list:
+ *                  RemoteGrainDirectory.cs:83-88, GrainDirectoryPartition.cs:427-434)
+ *   GD_LM_HOST     a changed GD_ACT_MULTI entry (its instance list lives in C#) or any KeyExt-category key
+ *                  (the KeyExt partition carries no VersionTags): answered in C#
+ * The equality test comes first, so an unchanged multi-activation entry is GD_LM_SAME. */
+#define GD_LM_SAME    0
+#define GD_LM_ABSENT  1
+#define GD_LM_UPDATED 2
+#define GD_LM_HOST    3
+int gd_dir_lookup_many_device(gd_handle* h, const gd_key* d_keys, const int32_t* d_etags, uint32_t n,
+                              uint8_t* d_kind, gd_val* d_vals, int32_t* d_tags);
+int gd_dir_lookup_many(gd_handle* h, const gd_key* keys, const int32_t* etags, uint32_t n, uint8_t* out_kind,
+                       gd_val* out_vals, int32_t* out_tags);
+
+/* The response, ProcessCacheRefreshResponse per item in batch order at `now`:
+ *   GD_LM_UPDATED  AddOrUpdate(key, value, tag): LRU.Add -- AdjustSize, then a new entry with a new
+ *                  generation, LastRefreshed = now, ExpirationTimer = initial, NumAccesses = 0; a value of
+ *                  silo GD_NO_SILO is the empty address list (dumps show it as {GD_NO_ACTIVATION, 0xFFFF};
+ *                  routes miss on it)
+ *   GD_LM_ABSENT   Remove
+ *   GD_LM_SAME     MarkAsFresh (AdaptiveGrainDirectoryCache.cs:127-136): if still cached, the next
+ *                  generation, ExpirationTimer = min(max, (long)((double)timer * growth)), LastRefreshed = now
+ *   GD_LM_HOST     skipped
+ * out_status (may be NULL) says what happened.  Keys of one batch are distinct: two items that find one
+ * cached entry are GD_EINVAL and change nothing.  ext (may be NULL) keys KeyExt entries as gd_cache_add_ext.
+ * A batch without UPDATED items runs on the device with no host round trip before its results; one with
+ * them goes through the add path's host simulation and is exact under eviction (an UPDATED item's
+ * AdjustSize may evict a key whose SAME comes later: GD_CR_NOT_PRESENT).  The device form applies the SAME /
+ * ABSENT / HOST items only and marks UPDATED ones GD_CR_DEFERRED for the host form; a duplicate there
+ * changes nothing and is reported by the call's return after it synchronises. */
+#define GD_CR_UPDATED     0
+#define GD_CR_REMOVED     1
+#define GD_CR_NOT_PRESENT 2
+#define GD_CR_FRESHENED   3
+#define GD_CR_SKIPPED     4
+#define GD_CR_DEFERRED    5
+int gd_cache_refresh_apply_device(gd_handle* h, int64_t now, const gd_key* d_keys, const gd_key_ext* d_ext,
+                                  const uint8_t* d_kind, uint32_t n, uint8_t* d_status);
+int gd_cache_refresh_apply(gd_handle* h, int64_t now, const gd_key* keys, const gd_key_ext* ext, const uint8_t* kind,
+                           const gd_val* vals, const int32_t* tags, uint32_t n, uint8_t* out_status);
+
 /* ---- membership change: IsValidSilo, VersionTag, silo removal, handoff merge ----
  * GrainDirectoryPartition.IsValidSilo (GrainDirectoryPartition.cs:242-245, the membership oracle's
  * IsFunctionalDirectory): valid[s] != 0 for every silo index s < n_silos that is a functional

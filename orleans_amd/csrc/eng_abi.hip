@@ -131,6 +131,9 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->kx_buf) free_buf(b);
     free_buf(h->cache_valid);
     if (h->cslots) (void)hipFree(h->cslots);
+    if (h->cage) (void)hipFree(h->cage);
+    for (DevBuf& b : h->cm_own) free_buf(b);
+    for (DevBuf& b : h->cm_scr) free_buf(b);
     free_buf(h->cx_heap);
     free_buf(h->cxi_tab);
     free_buf(h->cx8_tab);

@@ -82,6 +82,13 @@ int cache_rehash(gd_handle* h, unsigned long long cap) {
     hipError_t e = hipMalloc(&ns, cap * sizeof(CacheSlot));
     if (e != hipSuccess) return set_err(h, GD_ENOMEM, "cache hipMalloc(%llu slots): %s", cap, hipGetErrorString(e));
     HIP_TRY(h, hipMemsetAsync(ns, 0, cap * sizeof(CacheSlot), h->stream));
+    CacheAge* na = nullptr;
+    e = hipMalloc(&na, cap * sizeof(CacheAge));
+    if (e != hipSuccess) {
+        (void)hipFree(ns);
+        return set_err(h, GD_ENOMEM, "cache hipMalloc(%llu ages): %s", cap, hipGetErrorString(e));
+    }
+    HIP_TRY(h, hipMemsetAsync(na, 0, cap * sizeof(CacheAge), h->stream));
     CacheCounters c{};
     GD_TRY(cache_pull(h, &c));
     CacheCounters fresh = c;
@@ -91,11 +98,13 @@ int cache_rehash(gd_handle* h, unsigned long long cap) {
     HIP_TRY(h, hipMemcpyAsync(h->cctr, &fresh, sizeof fresh, hipMemcpyHostToDevice, h->stream));
     if (h->cslots) {
         GD_TRY(launch(h, "k_cache_rehash", dim3(blocks_for(h->ccap, BLOCK)), dim3(BLOCK), 0, k_cache_rehash,
-                      (const CacheSlot*)h->cslots, h->ccap, ns, cap - 1, h->cctr));
+                      (const CacheSlot*)h->cslots, h->ccap, ns, cap - 1, h->cctr, (const CacheAge*)h->cage, na));
         GD_TRY(sync(h));
         HIP_TRY(h, hipFree(h->cslots));
+        HIP_TRY(h, hipFree(h->cage));
     }
     h->cslots = ns;
+    h->cage = na;
     h->ccap = cap;
     return sync(h);
 }
@@ -189,6 +198,8 @@ int gd_cache_configure(gd_handle* h, uint32_t max_size, const uint8_t* local_sil
     if (h->cslots) {
         HIP_TRY(h, hipFree(h->cslots));
         h->cslots = nullptr;
+        HIP_TRY(h, hipFree(h->cage));
+        h->cage = nullptr;
     }
     const unsigned long long cap = pow2_at_least(2ull * max_size);
     h->cache_max = max_size;
@@ -297,13 +308,30 @@ int cx_reserve(gd_handle* h, uint64_t need) {
     return GD_OK;
 }
 
-// AddOrUpdate of a batch (LRU.Add, LRU.cs:71-76,165-182), KeyExt entries keyed by their string.
-int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, const gd_val* vals,
-                   const int32_t* versions, uint32_t n) {
+// AdaptiveGrainDirectoryCache.MarkAsFresh's new timer (:132): min(max, (long)((double)timer * growth)).
+static int64_t grown_timer(const gd_handle* h, int64_t timer) {
+    return std::min<int64_t>(h->cm_max, (int64_t)((double)timer * h->cm_growth));
+}
+
+// AddOrUpdate of a batch (LRU.Add, LRU.cs:71-76,165-182), KeyExt entries keyed by their string.  With
+// kinds (gd_cache_refresh_apply, ProcessCacheRefreshResponse): per item GD_LM_UPDATED = AddOrUpdate (an
+// empty address list, silo GD_NO_SILO, is cached as such), GD_LM_ABSENT = Remove, GD_LM_SAME = MarkAsFresh,
+// GD_LM_HOST = skipped; out_status[i] what happened.  Every new entry takes the cache clock.
+int cache_batch_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, const uint8_t* kinds, const gd_val* vals,
+                     const int32_t* versions, uint32_t n, uint8_t* out_status) {
     GD_TRY(cache_check(h));
     if (n && (!keys || !vals || !versions)) return set_err(h, GD_EINVAL, "null argument");
-    for (uint32_t i = 0; i < n; ++i)
+    std::vector<gd_val> fixed;                  // the empty address list's stored form
+    for (uint32_t i = 0; i < n; ++i) {
+        if (kinds && kinds[i] != GD_LM_UPDATED) continue;
+        if (kinds && vals[i].silo == GD_NO_SILO) {
+            if (fixed.empty()) fixed.assign(vals, vals + n);
+            fixed[i] = gd_val{GD_NO_ACTIVATION, 0xFFFFu};
+            continue;
+        }
         if (vals[i].silo > 0xFFFEu) return set_err(h, GD_EINVAL, "silo index %u out of range at %u", vals[i].silo, i);
+    }
+    if (!fixed.empty()) vals = fixed.data();
     if (n == 0) return GD_OK;
     HIP_TRY(h, hipSetDevice(h->device));
     HostExt hx;
@@ -319,6 +347,24 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
     // 1. where each key lives now
     std::vector<uint32_t> slot_of;
     GD_TRY(cache_find_batch(h, keys, ext, n, &slot_of));
+    std::vector<CacheAge> age_of;
+    if (kinds) {
+        // a refresh response holds one item per grain: two items on one cached entry refuse the batch
+        std::unordered_map<uint32_t, uint32_t> seen;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (kinds[i] == GD_LM_HOST || slot_of[i] == NONE32) continue;
+            auto r = seen.emplace(slot_of[i], i);
+            if (!r.second)
+                return set_err(h, GD_EINVAL, "refresh response: items %u and %u name one cached entry", r.first->second, i);
+        }
+        GD_TRY(ensure(h, h->cbuf[0], (size_t)n * sizeof(CacheAge)));
+        GD_TRY(launch(h, "k_cache_age_of", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_cache_age_of,
+                      (const uint32_t*)h->cbuf[4].p, n, (const CacheAge*)h->cage, (CacheAge*)h->cbuf[0].p));
+        age_of.resize(n);
+        HIP_TRY(h, hipMemcpyAsync(age_of.data(), h->cbuf[0].p, (size_t)n * sizeof(CacheAge), hipMemcpyDeviceToHost,
+                                  h->stream));
+        GD_TRY(sync(h));
+    }
     // 2. eviction candidates: each add evicts at most one entry and renews at most one, so the
     //    2n lowest generations cover every pre-existing entry this batch can evict
     const uint64_t M = h->cache_max;
@@ -332,6 +378,8 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
         uint64_t gen;
         uint32_t from_slot;   // pre-existing slot this entry renews, or NONE32
         bool alive;
+        bool fresh = false;   // a pre-existing entry MarkAsFresh only touched: value, ETag and NumAccesses stay
+        int64_t timer = -1;   // ... and its new ExpirationTimer; an entry this batch made: >= 0 once freshened
     };
     std::vector<Ent> ents;
     ents.reserve(n);
@@ -342,6 +390,42 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
     size_t vp = 0;
     uint64_t count = c.live, ng = c.next_gen;
     for (uint32_t i = 0; i < n; ++i) {
+        const uint8_t kind = kinds ? kinds[i] : (uint8_t)GD_LM_UPDATED;
+        if (kind != GD_LM_UPDATED) {
+            uint8_t st = GD_CR_SKIPPED;
+            if (kind == GD_LM_ABSENT || kind == GD_LM_SAME) {
+                auto it = ent_of.find(cache_key(keys[i], hx.s[i], hx.len[i]));
+                Ent* e = (it != ent_of.end() && ents[it->second].alive) ? &ents[it->second] : nullptr;
+                const bool in_slot = !e && it == ent_of.end() && slot_of[i] != NONE32 && !pre.count(slot_of[i]);
+                st = GD_CR_NOT_PRESENT;
+                if (kind == GD_LM_ABSENT && e) {                    // Remove (:82-86)
+                    e->alive = false;
+                    --count;
+                    st = GD_CR_REMOVED;
+                } else if (kind == GD_LM_ABSENT && in_slot) {
+                    pre[slot_of[i]] = 1;
+                    --count;
+                    st = GD_CR_REMOVED;
+                } else if (kind == GD_LM_SAME && e) {               // MarkAsFresh (:127-136)
+                    e->gen = ++ng;
+                    e->timer = grown_timer(h, e->timer >= 0 ? e->timer : h->cm_initial);
+                    heap.push({e->gen, it->second});
+                    st = GD_CR_FRESHENED;
+                } else if (kind == GD_LM_SAME && in_slot) {
+                    pre[slot_of[i]] = 2;
+                    Ent f{i, 0, 0, 0, ++ng, slot_of[i], true};
+                    f.fresh = true;
+                    f.timer = grown_timer(h, age_of[i].timer);
+                    ents.push_back(f);
+                    ent_of[cache_key(keys[i], hx.s[i], hx.len[i])] = (uint32_t)ents.size() - 1;
+                    heap.push({ng, (uint32_t)ents.size() - 1});
+                    st = GD_CR_FRESHENED;
+                }
+            }
+            if (out_status) out_status[i] = st;
+            continue;
+        }
+        if (out_status) out_status[i] = GD_CR_UPDATED;
         while (count >= M) {
             while (vp < victims.size() && pre.count(victims[vp].second)) ++vp;
             if (vp < victims.size()) {
@@ -372,6 +456,8 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
             e.silo = vals[i].silo;
             e.ver = versions[i];
             e.gen = ++ng;
+            e.fresh = false;                    // a new entry in its place
+            e.timer = -1;
             heap.push({e.gen, it->second});
         } else if (it == ent_of.end() && slot_of[i] != NONE32 && !pre.count(slot_of[i])) {
             pre[slot_of[i]] = 2;
@@ -396,12 +482,13 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
     for (const auto& p : pre)
         if (p.second == 1) ops.push_back(CacheOp{p.first, 0, 0, 0, 0, 0, 0});
     for (const Ent& e : ents) {
-        if (e.from_slot != NONE32)
-            ops.push_back(e.alive ? CacheOp{e.from_slot, 1, e.act, e.silo, e.gen, e.ver, 0}
-                                  : CacheOp{e.from_slot, 0, 0, 0, 0, 0, 0});
-        else if (e.alive) {
+        if (e.from_slot != NONE32) {
+            if (!e.alive) ops.push_back(CacheOp{e.from_slot, 0, 0, 0, 0, 0, 0});
+            else if (e.fresh) ops.push_back(CacheOp{e.from_slot, 2, 0, 0, e.gen, 0, 0, (long long)e.timer});
+            else ops.push_back(CacheOp{e.from_slot, 1, e.act, e.silo, e.gen, e.ver, 0, (long long)(e.timer + 1)});
+        } else if (e.alive) {
             ins_keys.push_back(keys[e.item]);
-            ins.push_back(CacheOp{NONE32, 1, e.act, e.silo, e.gen, e.ver, 0});
+            ins.push_back(CacheOp{NONE32, 1, e.act, e.silo, e.gen, e.ver, 0, (long long)(e.timer + 1)});
             ins_item.push_back(e.item);
             const int32_t len = hx.len[e.item];
             ins_x.push_back(len >= 0 ? hx.uh[e.item] : 0u);
@@ -414,7 +501,8 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
     if (!ops.empty()) {
         GD_TRY(h2d(h, h->cbuf[4], ops.data(), ops.size()));
         GD_TRY(launch(h, "k_cache_apply", dim3(blocks_for(ops.size(), BLOCK)), dim3(BLOCK), 0, k_cache_apply,
-                      (const CacheOp*)h->cbuf[4].p, (uint32_t)ops.size(), h->cslots, h->cctr));
+                      (const CacheOp*)h->cbuf[4].p, (uint32_t)ops.size(), h->cslots, h->cctr, h->cage,
+                      (long long)h->cm_clock, (long long)h->cm_initial));
     }
     if (xbytes) {                                        // after the evictions: their strings are dropped
         GD_TRY(cx_reserve(h, xbytes));
@@ -439,7 +527,7 @@ int cache_add_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, cons
         GD_TRY(launch(h, "k_cache_insert", dim3(blocks_for(ins.size(), BLOCK)), dim3(BLOCK), 0, k_cache_insert,
                       (const gd_key*)h->cbuf[3].p, (const CacheOp*)h->cbuf[5].p,
                       any_x ? (const uint32_t*)h->cbuf[6].p : (const uint32_t*)nullptr, (uint32_t)ins.size(),
-                      h->cslots, h->ccap - 1, h->cctr));
+                      h->cslots, h->ccap - 1, h->cctr, h->cage, (long long)h->cm_clock, (long long)h->cm_initial));
     }
     GD_TRY(sync(h));
     CacheCounters after{};
@@ -474,7 +562,8 @@ int cache_remove_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, u
     if (!ops.empty()) {
         GD_TRY(h2d(h, h->cbuf[6], ops.data(), ops.size()));
         GD_TRY(launch(h, "k_cache_apply", dim3(blocks_for(ops.size(), BLOCK)), dim3(BLOCK), 0, k_cache_apply,
-                      (const CacheOp*)h->cbuf[6].p, (uint32_t)ops.size(), h->cslots, h->cctr));
+                      (const CacheOp*)h->cbuf[6].p, (uint32_t)ops.size(), h->cslots, h->cctr, h->cage,
+                      (long long)h->cm_clock, (long long)h->cm_initial));
     }
     return sync(h);
 }
@@ -519,13 +608,13 @@ int cache_lookup_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, u
 extern "C" {
 
 int gd_cache_add(gd_handle* h, const gd_key* keys, const gd_val* vals, const int32_t* versions, uint32_t n) {
-    return cache_add_impl(h, keys, nullptr, vals, versions, n);
+    return cache_batch_impl(h, keys, nullptr, nullptr, vals, versions, n, nullptr);
 }
 
 int gd_cache_add_ext(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, const gd_val* vals,
                      const int32_t* versions, uint32_t n) {
     if (!h || (n && !ext_ok(ext, n))) return set_err(h, GD_EINVAL, "null argument");
-    return cache_add_impl(h, keys, ext, vals, versions, n);
+    return cache_batch_impl(h, keys, ext, nullptr, vals, versions, n, nullptr);
 }
 
 int gd_cache_remove(gd_handle* h, const gd_key* keys, uint32_t n, uint8_t* out_removed) {
@@ -553,6 +642,7 @@ int gd_cache_clear(gd_handle* h) {
     HIP_TRY(h, hipSetDevice(h->device));
     // LRU.Clear (:94-106) empties the dictionary; nextGeneration and the statistics stay
     HIP_TRY(h, hipMemsetAsync(h->cslots, 0, h->ccap * sizeof(CacheSlot), h->stream));
+    HIP_TRY(h, hipMemsetAsync(h->cage, 0, h->ccap * sizeof(CacheAge), h->stream));
     h->cx_used = 0;
     CacheCounters c{};
     GD_TRY(cache_pull(h, &c));

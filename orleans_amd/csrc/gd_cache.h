@@ -35,9 +35,19 @@ struct alignas(64) CacheSlot {
     uint32_t xuh;                // KeyExt entry: uniform hash of ToByteArray() (the home slot's hash)
     uint32_t xlen1;              // 0 = a three-word key (KeyExt null included); else KeyExt length + 1
     uint32_t xoff;               // KeyExt entry: byte offset of the string in the cache heap (16-B aligned)
-    uint32_t pad[2];
+    uint32_t nacc;               // the entry's NumAccesses (AdaptiveGrainDirectoryCache.cs:25; gd_maintain.h)
+    uint32_t pad;
 };
 static_assert(sizeof(CacheSlot) == 64, "cache slot must be 64 bytes");
+
+// The entry's two times, in an array parallel to the slots (as vtag is to the directory table): LastRefreshed
+// (DateTime ticks) and ExpirationTimer (ticks), AdaptiveGrainDirectoryCache.cs:15-17.  Created (:13) is
+// written by the reference and never read on this path: it is not stored.
+struct alignas(16) CacheAge {
+    long long refreshed;
+    long long timer;
+};
+static_assert(sizeof(CacheAge) == 16, "cache age must be 16 bytes");
 
 struct CacheCounters {
     unsigned long long next_gen;   // LRU.nextGeneration
@@ -322,13 +332,15 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_lookup(const gd_key* __r
 }
 
 // pos = inclusive scan of the hit flags: hit k of the batch gets generation next_gen + k
-// (TryGetValue's Interlocked.Increment in batch order); the last hit of a key wins.
+// (TryGetValue's Interlocked.Increment in batch order); the last hit of a key wins.  Each hit is
+// also one tmp.NumAccesses++ on its entry (AdaptiveGrainDirectoryCache.cs:106), duplicates counted each.
 static __global__ void __launch_bounds__(BLOCK) k_cache_touch(const uint32_t* __restrict__ cslot,
                                                        const uint32_t* __restrict__ pos, uint32_t n, CacheSlot* slots,
                                                        const CacheCounters* ctr) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n || cslot[i] == NONE32) return;
     atomicMax(&slots[cslot[i]].gen, ctr->next_gen + pos[i]);
+    atomicAdd(&slots[cslot[i]].nacc, 1u);
 }
 
 static __global__ void k_cache_advance(const uint32_t* __restrict__ pos, uint32_t n, CacheCounters* ctr) {
@@ -352,6 +364,13 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_find(const gd_key* __res
     const bool h = cache_find_msg(cache, keys, ext, i, slot, act, meta);
     slot_of[i] = h ? slot : NONE32;
     gen_of[i] = h ? cache.slots[slot].gen : 0ull;
+}
+
+// LastRefreshed / ExpirationTimer of each found slot (zeros when absent).
+static __global__ void __launch_bounds__(BLOCK) k_cache_age_of(const uint32_t* __restrict__ slot_of, uint32_t n,
+                                                        const CacheAge* __restrict__ age, CacheAge* __restrict__ out) {
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < n) out[i] = slot_of[i] == NONE32 ? CacheAge{0, 0} : age[slot_of[i]];
 }
 
 // Live entries with generation <= t: count, then collect (gen, slot) in any order.
@@ -386,7 +405,10 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_collect_le(const CacheSl
     }
 }
 
-// Outcome of an add batch on existing slots: kind 0 = evict (tombstone), 1 = update in place.
+// Outcome of an add batch on existing slots: kind 0 = evict (tombstone), 1 = update in place (a new
+// entry: LastRefreshed = now, ExpirationTimer = initial, NumAccesses = 0; aux != 0: the batch freshened it
+// afterwards and its timer is aux - 1), 2 = MarkAsFresh (the generation, LastRefreshed = now and the
+// timer in `aux`; value, ETag and NumAccesses stay).
 struct CacheOp {
     uint32_t slot;
     uint32_t kind;
@@ -395,10 +417,12 @@ struct CacheOp {
     unsigned long long gen;
     int32_t version;
     uint32_t pad;
+    long long aux;
 };
 
 static __global__ void __launch_bounds__(BLOCK) k_cache_apply(const CacheOp* __restrict__ ops, uint32_t n, CacheSlot* slots,
-                                                       CacheCounters* ctr) {
+                                                       CacheCounters* ctr, CacheAge* age, long long now,
+                                                       long long initial) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const CacheOp op = ops[i];
@@ -407,11 +431,16 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_apply(const CacheOp* __r
         s.meta = make_meta(SLOT_TOMB, 0);
         atomicAdd(&ctr->live, ~0ull);
         atomicAdd(&ctr->tomb, 1ull);
+    } else if (op.kind == 2) {
+        s.gen = op.gen;
+        age[op.slot] = CacheAge{now, op.aux};
     } else {
         s.act = op.act;
         s.gen = op.gen;
         s.version = op.version;
+        s.nacc = 0;
         s.meta = make_meta(SLOT_LIVE, op.silo);
+        age[op.slot] = CacheAge{now, op.aux ? op.aux - 1 : initial};
     }
 }
 
@@ -420,7 +449,8 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_apply(const CacheOp* __r
 static __global__ void __launch_bounds__(BLOCK) k_cache_insert(const gd_key* __restrict__ keys,
                                                         const CacheOp* __restrict__ vals,
                                                         const uint32_t* __restrict__ xm, uint32_t n, CacheSlot* slots,
-                                                        unsigned long long mask, CacheCounters* ctr) {
+                                                        unsigned long long mask, CacheCounters* ctr, CacheAge* age,
+                                                        long long now, long long initial) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
     const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
@@ -443,6 +473,8 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_insert(const gd_key* __r
             d.xuh = xuh;
             d.xlen1 = xlen1;
             d.xoff = xoff;
+            d.nacc = 0;
+            age[s] = CacheAge{now, vals[i].aux ? vals[i].aux - 1 : initial};
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __hip_atomic_store(mp, make_meta(SLOT_LIVE, vals[i].silo), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             atomicMax(&ctr->max_probe, dist);
@@ -456,10 +488,11 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_insert(const gd_key* __r
     atomicOr(&ctr->err, 2u);
 }
 
-// Live entries into a fresh table (tombstone compaction / growth).
+// Live entries into a fresh table (tombstone compaction / growth), their times with them.
 static __global__ void __launch_bounds__(BLOCK) k_cache_rehash(const CacheSlot* __restrict__ old_slots,
                                                         unsigned long long old_cap, CacheSlot* slots,
-                                                        unsigned long long mask, CacheCounters* ctr) {
+                                                        unsigned long long mask, CacheCounters* ctr,
+                                                        const CacheAge* __restrict__ old_age, CacheAge* age) {
     const unsigned long long j = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
     if (j >= old_cap) return;
     const CacheSlot sl = old_slots[j];
@@ -472,6 +505,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cache_rehash(const CacheSlot* 
             CacheSlot d = sl;
             d.meta = make_meta(SLOT_CLAIMED, 0);
             slots[s] = d;
+            age[s] = old_age[j];
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __hip_atomic_store(&slots[s].meta, sl.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             atomicMax(&ctr->max_probe, dist);

@@ -107,6 +107,18 @@ struct gd_handle {
     uint32_t cache_nsilos = 0;
     DevBuf cache_local, cache_valid;
     DevBuf cbuf[8];                   // cache scratch
+    // the cache's adaptive state and its maintainer (gd_maintain.h, eng_maintain.hip)
+    CacheAge* cage = nullptr;         // LastRefreshed / ExpirationTimer per cache slot (beside cslots)
+    int64_t cm_initial = 300000000, cm_max = 2400000000ll;   // initial / maximum ExpirationTimer in ticks (30 s, 240 s)
+    double cm_growth = 2.0;           // exponentialTimerGrowth
+    int64_t cm_clock = 0;             // the cache clock: DateTime.UtcNow of the add path (gd_cache_clock_set)
+    uint64_t cm_ring_gen = ~0ull;     // layout_gen the compact owner table was built at
+    uint32_t cm_nown = 0;             // distinct ring owners
+    DevBuf cm_own[2];                 // compact owner index per ring position; silo of each compact owner
+    DevBuf cm_scr[16];                // scan / apply scratch and the last scan's lists (held until the next scan)
+    uint32_t cm_scan_n = 0, cm_scan_owners = 0;   // the held lists' sizes
+    uint64_t cm_scan_bytes = 0;
+    bool cm_scan_valid = false;
     DevBuf shard_dest, shard_hist;    // exchange partition scratch
     DevBuf shard_n1;                  // low N1 words of the batch (k_shard_hist -> k_shard_gather, compact u32)
     bool shard_n1_copy = true;        // GD_SHARD_N1=0: the gather reads N1 from the 24-B keys
@@ -519,6 +531,10 @@ int fan_route(gd_handle* h, const uint32_t* row_off, const uint32_t* dst, const 
               uint32_t total, uint64_t tcd, uint32_t* target, uint32_t* sender, uint32_t* silo, uint32_t* act,
               uint8_t* status, const uint32_t* d_nf = nullptr, bool dev_total = false);
 int cache_pull(gd_handle* h, CacheCounters* c);
+CacheArgs cache_args(gd_handle* h);
+// AddOrUpdate / Remove / MarkAsFresh of a batch in order (kinds NULL: every item an add); eng_cache.hip.
+int cache_batch_impl(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, const uint8_t* kinds, const gd_val* vals,
+                     const int32_t* versions, uint32_t n, uint8_t* out_status);
 int cache_touch(gd_handle* h, uint32_t* hit, const uint32_t* cslot, uint32_t n);
 int split_emit(gd_handle* h, int move, gd_key* d_keys, gd_val* d_vals);
 int set_bitset(gd_handle* h, DevBuf& b, const std::vector<uint32_t>& bits);

@@ -99,6 +99,9 @@ EXPORTED_SYMBOLS = [
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
     "gd_collect_scan_all_device", "gd_collect_scan_all", "gd_collect_count_recent_device", "gd_collect_count_recent",
+    "gd_cache_maintain_configure", "gd_cache_clock_set", "gd_cache_entries_age", "gd_cache_scan_device", "gd_cache_scan",
+    "gd_cache_scan_fetch", "gd_dir_lookup_many_device", "gd_dir_lookup_many", "gd_cache_refresh_apply_device",
+    "gd_cache_refresh_apply",
 ]
 
 
@@ -215,6 +218,17 @@ GD_KEYEXT_NULL = -1
 GD_KEYEXT_HOST = -2
 
 
+class gd_cache_scan_result(C.Structure):
+    _fields_ = [("counts", C.c_uint64 * 5), ("n_owners", C.c_uint32), ("n", C.c_uint32), ("ext_bytes_len", C.c_uint64),
+                ("owner", C.c_void_p), ("offsets", C.c_void_p), ("keys", C.c_void_p), ("etags", C.c_void_p),
+                ("slots", C.c_void_p), ("ext_len", C.c_void_p), ("ext_off", C.c_void_p), ("ext_bytes", C.c_void_p)]
+
+
+GD_CM_SEEN, GD_CM_SELF_OWNED, GD_CM_FRESH, GD_CM_DROPPED, GD_CM_REFRESH = range(5)
+GD_LM_SAME, GD_LM_ABSENT, GD_LM_UPDATED, GD_LM_HOST = range(4)
+GD_CR_UPDATED, GD_CR_REMOVED, GD_CR_NOT_PRESENT, GD_CR_FRESHENED, GD_CR_SKIPPED, GD_CR_DEFERRED = range(6)
+
+
 class gd_key_ext(C.Structure):
     _fields_ = [("bytes", C.c_void_p), ("offset", C.c_void_p), ("length", C.c_void_p), ("bytes_len", C.c_uint64)]
 
@@ -248,6 +262,10 @@ GD_MULTI_RETURN_ROUTES = 1
 GD_MULTI_KEYS_READY = 2
 GD_MULTI_FORWARD = 4
 GD_MULTI_NO_KEYS = 8
+
+
+class ScanLists(dict):
+    """cache_scan's request lists: owner silo -> (keys, etags, exts) in list order; .owners, .offsets, .slots the CSR."""
 
 
 class GrainDispatchError(RuntimeError):
@@ -302,6 +320,16 @@ def _load() -> C.CDLL:
         "gd_dir_unregister_device": (C.c_int, [P, P, P, U32, P]),
         "gd_dir_set_valid_silos": (C.c_int, [P, P, U32]),
         "gd_dir_lookup_tagged": (C.c_int, [P, P, U32, P, P, P]),
+        "gd_cache_maintain_configure": (C.c_int, [P, C.c_int64, C.c_int64, C.c_double, C.c_int64]),
+        "gd_cache_clock_set": (C.c_int, [P, C.c_int64]),
+        "gd_cache_entries_age": (C.c_int, [P, P, P, P, U64, C.POINTER(U64)]),
+        "gd_cache_scan_device": (C.c_int, [P, C.c_int64, C.POINTER(gd_cache_scan_result)]),
+        "gd_cache_scan": (C.c_int, [P, C.c_int64, P, C.POINTER(U32), C.POINTER(U32), C.POINTER(U64)]),
+        "gd_cache_scan_fetch": (C.c_int, [P, P, P, P, P, P, P, P, P, U32, U32, U64]),
+        "gd_dir_lookup_many_device": (C.c_int, [P, P, P, U32, P, P, P]),
+        "gd_dir_lookup_many": (C.c_int, [P, P, P, U32, P, P, P]),
+        "gd_cache_refresh_apply_device": (C.c_int, [P, C.c_int64, P, C.POINTER(gd_key_ext), P, U32, P]),
+        "gd_cache_refresh_apply": (C.c_int, [P, C.c_int64, P, C.POINTER(gd_key_ext), P, P, P, U32, P]),
         "gd_dir_remove_silos": (C.c_int, [P, P, U32, C.POINTER(U64), C.POINTER(U64), C.POINTER(U64)]),
         "gd_activation_ids_set": (C.c_int, [P, P, P, U32]),
         "gd_dir_merge": (C.c_int, [P, P, P, P, U32, P, P]),
@@ -1752,6 +1780,77 @@ class GrainDispatch:
                 key = key + (bytes(blob[int(xo[i]):int(xo[i]) + int(xl[i])]),)
             out[key] = (int(v[i, 0]), int(v[i, 1]), int(ver[i]), int(gen[i]))
         return out
+
+    # -- the directory cache's maintainer ------------------------------
+    def cache_maintain_configure(self, initial_ticks: int, max_ticks: int, growth: float, now: int):
+        self._c(lib.gd_cache_maintain_configure(self.h, initial_ticks, max_ticks, growth, now))
+
+    def cache_clock_set(self, now: int):
+        self._c(lib.gd_cache_clock_set(self.h, now))
+
+    def cache_entries_age(self):
+        """(refreshed i64, timer i64, num_accesses i32) in the slot order of cache_entries()."""
+        n = C.c_uint64(0)
+        self._c(lib.gd_cache_entries_age(self.h, None, None, None, 0, C.byref(n)))
+        m = n.value
+        r = np.zeros(max(m, 1), dtype=np.int64)
+        t = np.zeros(max(m, 1), dtype=np.int64)
+        a = np.zeros(max(m, 1), dtype=np.int32)
+        if m:
+            self._c(lib.gd_cache_entries_age(self.h, _ptr(r), _ptr(t), _ptr(a), m, C.byref(n)))
+        return r[:m], t[:m], a[:m]
+
+    def cache_scan(self, now: int):
+        """AdaptiveDirectoryCacheMaintainer.Run's loop at `now`.  Returns (counts, lists): counts the five
+        numbers (seen, self-owned, fresh, dropped, to refresh); lists an insertion-ordered dict owner silo ->
+        (keys u64[m, 3], etags i32[m], exts: list of bytes or None per key), with lists.slots the cache slots."""
+        counts = np.zeros(5, dtype=np.uint64)
+        no, n, nb = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        self._c(lib.gd_cache_scan(self.h, now, _ptr(counts), C.byref(no), C.byref(n), C.byref(nb)))
+        no, n, nb = no.value, n.value, nb.value
+        owner = np.zeros(max(no, 1), dtype=np.uint32)
+        offs = np.zeros(no + 1, dtype=np.uint32)
+        keys = np.zeros((max(n, 1), 3), dtype=np.uint64)
+        etags = np.zeros(max(n, 1), dtype=np.int32)
+        slots = np.zeros(max(n, 1), dtype=np.uint32)
+        xl = np.zeros(max(n, 1), dtype=np.int32)
+        xo = np.zeros(max(n, 1), dtype=np.uint64)
+        blob = np.zeros(max(nb, 1), dtype=np.uint8)
+        self._c(lib.gd_cache_scan_fetch(self.h, _ptr(owner), _ptr(offs), _ptr(keys), _ptr(etags), _ptr(slots), _ptr(xl),
+                                        _ptr(xo), _ptr(blob), no, n, nb))
+        lists = ScanLists()
+        lists.slots, lists.offsets, lists.owners = slots[:n].copy(), offs.copy(), owner[:no].copy()
+        for r in range(no):
+            a, b = int(offs[r]), int(offs[r + 1])
+            exts = [bytes(blob[int(xo[k]):int(xo[k]) + int(xl[k])]) if xl[k] >= 0 else None for k in range(a, b)]
+            lists[int(owner[r])] = (keys[a:b].copy(), etags[a:b].copy(), exts)
+        return [int(x) for x in counts], lists
+
+    def dir_lookup_many(self, keys, etags):
+        """LookUpMany: (kind u8, act u32, silo u32, tag i32) per item."""
+        k = keys_array(keys)
+        n = len(k)
+        e = np.ascontiguousarray(np.asarray(etags, dtype=np.int32))
+        kind = np.zeros(max(n, 1), dtype=np.uint8)
+        vals = np.zeros((max(n, 1), 2), dtype=np.uint32)
+        tags = np.zeros(max(n, 1), dtype=np.int32)
+        self._c(lib.gd_dir_lookup_many(self.h, _ptr(k), _ptr(e), n, _ptr(kind), _ptr(vals), _ptr(tags)))
+        return kind[:n], vals[:n, 0].copy(), vals[:n, 1].copy(), tags[:n]
+
+    def cache_refresh_apply(self, now: int, keys, kinds, acts, silos, tags, exts=None) -> np.ndarray:
+        """ProcessCacheRefreshResponse in batch order; returns the per-item GD_CR_* status."""
+        k = keys_array(keys)
+        n = len(k)
+        kind = np.ascontiguousarray(np.asarray(kinds, dtype=np.uint8))
+        vals = np.zeros((max(n, 1), 2), dtype=np.uint32)
+        vals[:n, 0] = acts
+        vals[:n, 1] = silos
+        t = np.ascontiguousarray(np.asarray(tags, dtype=np.int32))
+        st = np.zeros(max(n, 1), dtype=np.uint8)
+        x = None if exts is None else self._ext(exts, n)
+        self._c(lib.gd_cache_refresh_apply(self.h, now, _ptr(k), None if x is None else C.byref(x.struct), _ptr(kind),
+                                           _ptr(vals), _ptr(t), n, _ptr(st)))
+        return st[:n]
 
     # -- follower fan-out (SURVEY 8 f2) ----------------------------------------------
     def fanout_route_bucket(self, row_off, dst, frontier, type_code: int, n_act: Optional[int]):
