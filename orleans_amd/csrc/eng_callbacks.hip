@@ -35,11 +35,7 @@ int cb_pull(gd_handle* h, CbCounts* c, const char* call) {
         c->tomb += full.stripe[k][1];
     }
     if (!c->err) return GD_OK;
-    CbCounters* d = (CbCounters*)h->cb_ctr.p;
-    HIP_TRY(h, hipMemsetAsync(&d->err, 0, 4, h->stream));
-    if (c->err & ERR_UNSETTLED)     // votes may be left in the election words
-        HIP_TRY(h, hipMemsetAsync(h->cb_last.p, 0, (size_t)h->cb_cap * 8, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    GD_TRY(table_err_clear(h, &((CbCounters*)h->cb_ctr.p)->err, c->err, h->cb_last, h->cb_cap));
     if (c->err & CB_ERR_FULL) return set_err(h, GD_EFULL, "%s: the callback table is full (0x%x)", call, c->err);
     if (c->err & CB_ERR_SILO) return set_err(h, GD_EINVAL, "%s: a target silo index above 0xFFFE (0x%x)", call, c->err);
     return set_err(h, GD_ETIMEOUT, "%s: an earlier device batch did not settle (0x%x)", call, c->err);
@@ -47,64 +43,37 @@ int cb_pull(gd_handle* h, CbCounts* c, const char* call) {
 
 // A zeroed table of `cap` slots with its deadlines and election words.
 int cb_alloc(gd_handle* h, unsigned long long cap, DevBuf& tab, DevBuf& dl, DevBuf& last) {
-    int r = ensure(h, tab, (size_t)cap * sizeof(CbSlot));
-    if (r == GD_OK) r = ensure(h, dl, (size_t)cap * 8);
-    if (r == GD_OK) r = ensure(h, last, (size_t)cap * 8);
-    if (r != GD_OK) {
-        free_buf(tab);
-        free_buf(dl);
-        free_buf(last);
-        return set_err(h, GD_EFULL, "callback table: no memory for %llu slots", cap);
-    }
-    HIP_TRY(h, hipMemsetAsync(tab.p, 0, (size_t)cap * sizeof(CbSlot), h->stream));
-    HIP_TRY(h, hipMemsetAsync(last.p, 0, (size_t)cap * 8, h->stream));
-    return GD_OK;
+    return table_alloc(h, "callback", cap, sizeof(CbSlot), 8, tab, dl, last);
 }
 
 // Rebuild on the stream at `cap` slots: the `live` entries move, the tombstones go.
 int cb_rebuild(gd_handle* h, unsigned long long cap, uint32_t live) {
     if (cap > CB_MAX_CAP) return set_err(h, GD_EFULL, "callback table: more than 2^31 slots");
-    DevBuf tab, dl, last;
-    GD_TRY(cb_alloc(h, cap, tab, dl, last));
+    DevBuf fresh[3];
+    GD_TRY(cb_alloc(h, cap, fresh[0], fresh[1], fresh[2]));
     const CbTab old = cb_tab(h);
     const unsigned long long old_cap = h->cb_cap;
-    const CbTab nt{(CbSlot*)tab.p, (int64_t*)dl.p, cap - 1ull, old.ctr};
+    const CbTab nt{(CbSlot*)fresh[0].p, (int64_t*)fresh[1].p, cap - 1ull, old.ctr};
     GD_TRY(launch(h, "k_cb_rebuild", dim3(blocks_for(old_cap, BLOCK)), dim3(BLOCK), 0, k_cb_rebuild,
                   (const CbSlot*)old.slots, (const int64_t*)old.deadline, old_cap, nt));
     // the counts afterwards: `live` entries (the caller's read-back), no tombstone
     HIP_TRY(h, hipMemsetAsync(old.ctr->stripe, 0, sizeof(old.ctr->stripe), h->stream));
     HIP_TRY(h, hipMemsetD32Async((hipDeviceptr_t)&old.ctr->stripe[0][0], (int)live, 1, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_buf(h->cb_tab);
-    free_buf(h->cb_dl);
-    free_buf(h->cb_last);
-    h->cb_tab = tab;
-    h->cb_dl = dl;
-    h->cb_last = last;
-    h->cb_cap = cap;
-    return GD_OK;
+    return table_swap(h, {&h->cb_tab, &h->cb_dl, &h->cb_last}, fresh, h->cb_cap, cap);
 }
 
-// Room for `incoming` adds at load <= 0.75, counting tombstones.  Without a read-back while the bound kept on
-// the host (every add since the last read-back counted as a new slot) allows it; else the counters are read and,
-// if need be, the table is rebuilt: at the same capacity while the live entries fill at most half of it, else
-// at double (and on until the batch fits).
+// Room for `incoming` adds (table_reserve).
 int cb_reserve(gd_handle* h, uint64_t incoming, const char* call) {
-    if ((h->cb_used_ub + incoming) * 4 <= h->cb_cap * 3) {
-        h->cb_used_ub += incoming;
-        return GD_OK;
-    }
-    GD_TRY(check_not_capturing(h, call));
-    CbCounts c;
-    GD_TRY(cb_pull(h, &c, call));
-    if (((uint64_t)c.live + c.tomb + incoming) * 4 > h->cb_cap * 3) {
-        unsigned long long cap = (uint64_t)c.live * 2 <= h->cb_cap ? h->cb_cap : h->cb_cap * 2;
-        while (((uint64_t)c.live + incoming) * 4 > cap * 3) cap *= 2;
-        GD_TRY(cb_rebuild(h, cap, c.live));
-        c.tomb = 0;
-    }
-    h->cb_used_ub = (uint64_t)c.live + c.tomb + incoming;
-    return GD_OK;
+    return table_reserve(
+        h, h->cb_used_ub, h->cb_cap, incoming, call,
+        [&](uint64_t& live, uint64_t& tomb) {
+            CbCounts c;
+            GD_TRY(cb_pull(h, &c, call));
+            live = c.live;
+            tomb = c.tomb;
+            return (int)GD_OK;
+        },
+        [&](unsigned long long cap, uint64_t live) { return cb_rebuild(h, cap, (uint32_t)live); });
 }
 
 // ---- the batches on device arrays.  sync_passes: read-back driven passes (the host forms); else gated ones.
@@ -120,26 +89,12 @@ int add_device(gd_handle* h, const int64_t* ids, const uint32_t* handles, const 
     const CbTab t = cb_tab(h);
     uint32_t* last = cb_word(h, 0);
     const dim3 grid(blocks_for(n, BLOCK)), block(BLOCK);
-    HIP_TRY(h, hipMemsetAsync(t.ctr->retry, 0, sizeof(t.ctr->retry), h->stream));
-    GD_TRY(launch(h, "k_cb_claim", grid, block, 0, k_cb_claim, ids, n, t, slot_of, is_new, 0u, (const uint32_t*)nullptr,
-                  last));
     const uint32_t* unsettled = nullptr;
-    if (sync_passes) {
-        for (uint32_t p = 1;; ++p) {
-            uint32_t deferred = 0;
-            GD_TRY(read_back(h, &t.ctr->retry[(p - 1) % CB_PASSES], &deferred, 1));
-            if (!deferred) break;
-            if (p > 4096) return set_err(h, GD_ETIMEOUT, "%s: the claims did not settle", call);
-            HIP_TRY(h, hipMemsetAsync(&t.ctr->retry[p % CB_PASSES], 0, 4, h->stream));
-            GD_TRY(launch(h, "k_cb_claim", grid, block, 0, k_cb_claim, ids, n, t, slot_of, is_new, p,
-                          (const uint32_t*)nullptr, last));
-        }
-    } else {
-        for (uint32_t p = 1; p < CB_PASSES; ++p)
-            GD_TRY(launch(h, "k_cb_claim", grid, block, 0, k_cb_claim, ids, n, t, slot_of, is_new, p,
-                          (const uint32_t*)&t.ctr->retry[p - 1], last));
-        unsettled = &t.ctr->retry[CB_PASSES - 1];
-    }
+    GD_TRY(claim_pass_driver(h, t.ctr->retry, CB_PASSES, sync_passes, call, &unsettled,
+                             [&](uint32_t p, const uint32_t* gate, uint32_t*) {   // k_cb_claim finds its own word
+                                 return launch(h, "k_cb_claim", grid, block, 0, k_cb_claim, ids, n, t, slot_of, is_new, p,
+                                               gate, last);
+                             }));
     return launch(h, "k_cb_commit", grid, block, 0, k_cb_commit, handles, deadlines, n, t, (const uint32_t*)slot_of,
                   (const uint8_t*)is_new, last, unsettled, out_added);
 }

@@ -33,10 +33,7 @@ int gw_pull(gd_handle* h, int t, DevCounters* c, const char* call) {
     GD_TRY(fold_counters(h, d));
     GD_TRY(read_back(h, d, (uint32_t*)c, sizeof(DevCounters) / 4));
     if (!c->err) return GD_OK;
-    HIP_TRY(h, hipMemsetAsync(&d->err, 0, 4, h->stream));
-    if (c->err & ERR_UNSETTLED)     // votes may be left in the election words
-        HIP_TRY(h, hipMemsetAsync(h->gw_last[t].p, 0, (size_t)h->gw_cap[t] * 8, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    GD_TRY(table_err_clear(h, &d->err, c->err, h->gw_last[t], h->gw_cap[t]));
     const char* what = t == GW_CLIENTS ? "client" : "route";
     if (c->err & GW_ERR_FULL) return set_err(h, GD_EFULL, "%s: the gateway's %s table is full (0x%x)", call, what, c->err);
     return set_err(h, GD_ETIMEOUT, "%s: an earlier device batch did not settle in the %s table (0x%x)", call, what, c->err);
@@ -47,65 +44,43 @@ int gw_pull_both(gd_handle* h, const char* call) {
     return gw_pull(h, GW_ROUTES, &c, call);
 }
 
-// A zeroed table of `cap` slots with its values, counters and election words.
+// A zeroed table of `cap` slots with its values and election words.
 int gw_alloc(gd_handle* h, int t, unsigned long long cap, DevBuf& slots, DevBuf& side, DevBuf& last) {
-    int r = ensure(h, slots, (size_t)cap * sizeof(Slot));
-    if (r == GD_OK) r = ensure(h, side, (size_t)cap * side_bytes(t));
-    if (r == GD_OK) r = ensure(h, last, (size_t)cap * 8);
-    if (r != GD_OK) {
-        free_buf(slots);
-        free_buf(side);
-        free_buf(last);
-        return set_err(h, GD_EFULL, "gateway table: no memory for %llu slots", cap);
-    }
-    HIP_TRY(h, hipMemsetAsync(slots.p, 0, (size_t)cap * sizeof(Slot), h->stream));
-    HIP_TRY(h, hipMemsetAsync(last.p, 0, (size_t)cap * 8, h->stream));
-    return GD_OK;
+    return table_alloc(h, "gateway", cap, sizeof(Slot), side_bytes(t), slots, side, last);
 }
 
 // Rebuild on the stream at `cap` slots: the live entries move with their values, the tombstones go.
 int gw_rebuild(gd_handle* h, int t, unsigned long long cap) {
     if (cap > GW_MAX_CAP) return set_err(h, GD_EFULL, "gateway table: more than 2^31 slots");
-    DevBuf slots, side, last;
-    GD_TRY(gw_alloc(h, t, cap, slots, side, last));
+    DevBuf fresh[3];
+    GD_TRY(gw_alloc(h, t, cap, fresh[0], fresh[1], fresh[2]));
     const GwTab old = gw_tab(h, t);
     const unsigned long long old_cap = h->gw_cap[t];
     HIP_TRY(h, hipMemsetAsync(old.ctr, 0, CTR_BYTES, h->stream));      // k_gw_rehash counts live and max_probe anew
     const dim3 grid(blocks_for(old_cap, BLOCK)), block(BLOCK);
     if (t == GW_CLIENTS)
         GD_TRY(launch(h, "k_gw_rehash", grid, block, 0, k_gw_rehash<GwClient>, (const Slot*)old.slots,
-                      (const GwClient*)h->gw_side[t].p, old_cap, (Slot*)slots.p, (GwClient*)side.p, cap - 1ull, old.ctr));
+                      (const GwClient*)h->gw_side[t].p, old_cap, (Slot*)fresh[0].p, (GwClient*)fresh[1].p, cap - 1ull,
+                      old.ctr));
     else
         GD_TRY(launch(h, "k_gw_rehash", grid, block, 0, k_gw_rehash<int64_t>, (const Slot*)old.slots,
-                      (const int64_t*)h->gw_side[t].p, old_cap, (Slot*)slots.p, (int64_t*)side.p, cap - 1ull, old.ctr));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    free_buf(h->gw_slots[t]);
-    free_buf(h->gw_side[t]);
-    free_buf(h->gw_last[t]);
-    h->gw_slots[t] = slots;
-    h->gw_side[t] = side;
-    h->gw_last[t] = last;
-    h->gw_cap[t] = cap;
-    return GD_OK;
+                      (const int64_t*)h->gw_side[t].p, old_cap, (Slot*)fresh[0].p, (int64_t*)fresh[1].p, cap - 1ull,
+                      old.ctr));
+    return table_swap(h, {&h->gw_slots[t], &h->gw_side[t], &h->gw_last[t]}, fresh, h->gw_cap[t], cap);
 }
 
-// Room for `incoming` new entries at load <= 0.75, counting tombstones: the callback table's rule (cb_reserve).
+// Room for `incoming` new entries in table t (table_reserve).
 int gw_reserve(gd_handle* h, int t, uint64_t incoming, const char* call) {
-    if ((h->gw_used_ub[t] + incoming) * 4 <= h->gw_cap[t] * 3) {
-        h->gw_used_ub[t] += incoming;
-        return GD_OK;
-    }
-    GD_TRY(check_not_capturing(h, call));
-    DevCounters c;
-    GD_TRY(gw_pull(h, t, &c, call));
-    if ((c.live + c.tomb + incoming) * 4 > h->gw_cap[t] * 3) {
-        unsigned long long cap = c.live * 2 <= h->gw_cap[t] ? h->gw_cap[t] : h->gw_cap[t] * 2;
-        while ((c.live + incoming) * 4 > cap * 3) cap *= 2;
-        GD_TRY(gw_rebuild(h, t, cap));
-        c.tomb = 0;
-    }
-    h->gw_used_ub[t] = c.live + c.tomb + incoming;
-    return GD_OK;
+    return table_reserve(
+        h, h->gw_used_ub[t], h->gw_cap[t], incoming, call,
+        [&](uint64_t& live, uint64_t& tomb) {
+            DevCounters c;
+            GD_TRY(gw_pull(h, t, &c, call));
+            live = c.live;
+            tomb = c.tomb;
+            return (int)GD_OK;
+        },
+        [&](unsigned long long cap, uint64_t) { return gw_rebuild(h, t, cap); });
 }
 
 // The claim passes of a batch over table t: pass 0 (init: open's), then read-back driven ones (the host forms) or
@@ -116,24 +91,14 @@ int gw_claims(gd_handle* h, int t, const gd_key* keys, uint32_t n, uint32_t* slo
     uint32_t* retry = gw_state(h)->retry[t];
     const dim3 grid(blocks_for(n, BLOCK)), block(BLOCK);
     const uint32_t ea = elect_all ? 1u : 0u;
-    HIP_TRY(h, hipMemsetAsync(retry, 0, sizeof(uint32_t) * GW_PASSES, h->stream));
-    GD_TRY(launch(h, "k_gw_claim", grid, block, 0, k_gw_claim, keys, n, tab, slot_of, is_new, 0u, init ? 1u : 0u,
-                  (const uint32_t*)nullptr, &retry[0], win, ea));
-    if (sync_passes) {
-        for (uint32_t p = 1;; ++p) {
-            uint32_t deferred = 0;
-            GD_TRY(read_back(h, &retry[(p - 1) % GW_PASSES], &deferred, 1));
-            if (!deferred) return GD_OK;
-            if (p > 4096) return set_err(h, GD_ETIMEOUT, "%s: the claims did not settle", call);
-            HIP_TRY(h, hipMemsetAsync(&retry[p % GW_PASSES], 0, 4, h->stream));
-            GD_TRY(launch(h, "k_gw_claim", grid, block, 0, k_gw_claim, keys, n, tab, slot_of, is_new, p, 0u,
-                          (const uint32_t*)nullptr, &retry[p % GW_PASSES], win, ea));
-        }
-    }
-    for (uint32_t p = 1; p < GW_PASSES; ++p)
-        GD_TRY(launch(h, "k_gw_claim", grid, block, 0, k_gw_claim, keys, n, tab, slot_of, is_new, p, 0u,
-                      (const uint32_t*)&retry[p - 1], &retry[p], win, ea));
-    return launch(h, "k_gw_settled", dim3(1), dim3(WAVE), 0, k_gw_settled, tab.ctr, (const uint32_t*)&retry[GW_PASSES - 1]);
+    const uint32_t* unsettled = nullptr;
+    GD_TRY(claim_pass_driver(h, retry, GW_PASSES, sync_passes, call, &unsettled,
+                             [&](uint32_t p, const uint32_t* gate, uint32_t* word) {
+                                 return launch(h, "k_gw_claim", grid, block, 0, k_gw_claim, keys, n, tab, slot_of, is_new,
+                                               p, p == 0 && init ? 1u : 0u, gate, word, win, ea);
+                             }));
+    if (!unsettled) return GD_OK;
+    return launch(h, "k_gw_settled", dim3(1), dim3(WAVE), 0, k_gw_settled, tab.ctr, unsettled);
 }
 
 // ---- the batches on device arrays

@@ -52,19 +52,8 @@ static __global__ void __launch_bounds__(BLOCK) k_ad_find(const gd_key* __restri
                                                    uint32_t* __restrict__ slot_of, uint32_t* __restrict__ last) {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n) return;
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), t.mask);
-    uint32_t res = NONE32;
-    for (uint32_t p = 0; p <= t.ctr->max_probe; ++p) {
-        const Slot sl = t.slots[s];
-        const uint32_t st = slot_state(sl.meta);
-        if (st == SLOT_EMPTY) break;
-        if (st == SLOT_LIVE && sl.n0 == n0 && sl.n1 == n1 && sl.tcd == tcd) {
-            res = (uint32_t)s;
-            break;
-        }
-        s = (s + 1) & t.mask;
-    }
+    uint4 b;
+    const uint32_t res = find_slot(t.slots, t.mask, t.ctr->max_probe, keys[i].n0, keys[i].n1, keys[i].type_code_data, b);
     slot_of[i] = res;
     if (last && res != NONE32) atomicMax(&last[res], ~i);
 }

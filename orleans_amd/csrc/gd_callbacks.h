@@ -11,8 +11,8 @@
 //
 // States, claims and elections are gd_dirbatch.h's: EMPTY ends a chain, TOMB keeps it going and is the first
 // choice of an add, CLAIMED / PENDING exist only inside an add, and the `~i` first-wins word (one per slot) both
-// names a fresh claim's claimer and elects the batch item that commits.  cb_claim_item is reg_claim_item for an
-// 8-B key; nothing of gd_dirbatch.h is changed.
+// names a fresh claim's claimer and elects the batch item that commits.  The add and the rebuild run that
+// header's claim_walk and rehash_place over CbSlots, this table's policy: the 8-B key, cb_home, cb_meta.
 //
 // respond.  Ids do not interact, so a batch is the sequential loop once each id's own responses are ordered.
 // Among an id's responses that reach the table (not gatewayed back, not masked by `turn`) and find the entry at
@@ -134,86 +134,25 @@ __device__ __forceinline__ void cb_count(CbCounters* ctr, bool flag, int live_d,
 }
 
 // ------------------------------------------------------------------ add
-// reg_claim_item (gd_dirbatch.h) for an 8-B key: the id's slot, or a claim of its chain's first free slot (the
-// first tombstone, else the EMPTY slot ending it).  is_new: the entry is this batch's.
-__device__ __forceinline__ void cb_claim_item(uint32_t i, const int64_t* __restrict__ ids, CbSlot* slots,
-                                              unsigned long long mask, CbCounters* ctr, uint32_t* __restrict__ slot_of,
-                                              uint8_t* __restrict__ is_new, uint32_t* retry, bool& reused, uint32_t tag,
-                                              uint32_t* __restrict__ last, bool& claimed) {
-    const int64_t id = ids[i];
-    unsigned long long s = cb_home(id, mask), dist = 0;
-    uint32_t res = NONE32;
-    uint8_t fresh = 0;
-    unsigned long long tomb_s = ~0ull, tomb_dist = 0;
-    uint32_t tomb_meta = 0;
-    for (;;) {
-        const uint32_t meta = __hip_atomic_load(&slots[s].meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st = cb_state(meta);
-        const bool ends = st == SLOT_EMPTY || dist > mask;
-        if (ends && st != SLOT_EMPTY && tomb_s == ~0ull) {
-            atomicOr(&ctr->err, CB_ERR_FULL);                // no free slot (the host keeps the load <= 0.75)
-            break;
-        }
-        bool won = false;
-        const bool tomb = tomb_s != ~0ull;
-        const unsigned long long t = tomb ? tomb_s : s, d = tomb ? tomb_dist : dist;
-        if (ends) {
-            uint32_t expected = tomb ? tomb_meta : meta;
-            uint32_t* mp = &slots[t].meta;
-            won = __hip_atomic_compare_exchange_strong(mp, &expected, cb_meta(SLOT_CLAIMED, 0, 0), __ATOMIC_RELAXED,
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (won) {
-                atomicMax(&last[t], ~i);                     // the claimer, readable by this launch's walks
-                slots[t].id = id;
-                slots[t].handle = NONE32;
-                __hip_atomic_store(mp, cb_meta(SLOT_PENDING, 0, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        // keeps the winner's writes inside the loop, ahead of the losers' next read (see reg_claim_item)
-        __builtin_amdgcn_wave_barrier();
-        if (won) {
-            reused = tomb;
-            claimed = true;
-            res = (uint32_t)t;
-            fresh = 1;
-            break;
-        }
-        if (ends) {                                          // lost slot t: walk on from it
-            s = t;
-            dist = d;
-            tomb_s = ~0ull;
-            continue;
-        }
-        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && cb_silo(meta) == tag);
-        if (unpublished) {
-            const uint32_t w = __hip_atomic_load(&last[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (w == 0) {                                    // a claim not yet recorded: the next pass
-                res = SLOT_RETRY;
-                atomicAdd(retry, 1u);
-                break;
-            }
-            if (ids[~w] == id) {                             // the twin's claim: join it
-                res = (uint32_t)s;
-                fresh = 1;
-                break;
-            }
-        }
-        if (st == SLOT_TOMB && tomb_s == ~0ull) {
-            tomb_s = s;
-            tomb_meta = meta;
-            tomb_dist = dist;
-        }
-        if (!unpublished && (st == SLOT_LIVE || st == SLOT_PENDING) && slots[s].id == id) {
-            res = (uint32_t)s;                               // published before this launch
-            fresh = st == SLOT_PENDING ? 1 : 0;
-            break;
-        }
-        s = (s + 1) & mask;
-        ++dist;
+// The table to claim_walk and rehash_place (gd_dirbatch.h, DirSlots); PENDING's tag lies in the silo field.
+struct CbSlots {
+    using Key = int64_t;
+    CbSlot* slots;
+    unsigned long long mask;
+    __device__ __forceinline__ unsigned long long home(int64_t id) const { return cb_home(id, mask); }
+    __device__ __forceinline__ uint32_t* meta(unsigned long long s) const { return &slots[s].meta; }
+    static __device__ __forceinline__ uint32_t state(uint32_t meta) { return cb_state(meta); }
+    static __device__ __forceinline__ uint32_t tag(uint32_t meta) { return cb_silo(meta); }
+    static __device__ __forceinline__ uint32_t claimed() { return cb_meta(SLOT_CLAIMED, 0, 0); }
+    static __device__ __forceinline__ uint32_t pending(uint32_t tag) { return cb_meta(SLOT_PENDING, 0, tag); }
+    __device__ __forceinline__ void put(unsigned long long s, int64_t id) const {
+        slots[s].id = id;
+        slots[s].handle = NONE32;
     }
-    slot_of[i] = res;
-    is_new[i] = fresh;
-}
+    __device__ __forceinline__ bool holds(unsigned long long s, int64_t id) const { return slots[s].id == id; }
+    static __device__ __forceinline__ bool same(int64_t a, int64_t b) { return a == b; }
+};
+static_assert(CB_ERR_FULL == 2u, "claim_walk's table-full bit");
 
 // Pass 0: every item; pass p >= 1: the items pass p - 1 deferred, and only if it deferred any (gate = its count;
 // null: the host read it).  Counts its own deferred items into retry[pass % CB_PASSES], zeroed by the host.
@@ -223,10 +162,11 @@ static __global__ void __launch_bounds__(BLOCK) k_cb_claim(const int64_t* __rest
                                                     uint32_t* __restrict__ last) {
     if (gate && *gate == 0) return;
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    bool reused = false, claimed = false;
+    bool reused = false;
     if (i < n && (pass == 0 || slot_of[i] == SLOT_RETRY)) {
-        cb_claim_item(i, ids, tab.slots, tab.mask, tab.ctr, slot_of, is_new, &tab.ctr->retry[pass % CB_PASSES], reused,
-                      claim_tag(pass), last, claimed);
+        uint32_t pd = 0;                                     // this table keeps no max_probe
+        const bool claimed = claim_walk(CbSlots{tab.slots, tab.mask}, i, ids, &tab.ctr->err, slot_of, is_new,
+                                        &tab.ctr->retry[pass % CB_PASSES], pd, reused, claim_tag(pass), last);
         // the election (k_cb_commit); a claimer voted when it claimed
         if (is_new[i] && !claimed) atomicMax(&last[slot_of[i]], ~i);
     }
@@ -491,7 +431,7 @@ static __global__ void __launch_bounds__(BLOCK) k_cb_scan_emit(CbTab tab, CbScan
 }
 
 // ------------------------------------------------------------------ rebuild
-// Every live entry of the old table into the new, zeroed one (ids are distinct: a claimer compares no key).
+// Every live entry of the old table into the new, zeroed one.
 static __global__ void __launch_bounds__(BLOCK) k_cb_rebuild(const CbSlot* __restrict__ old_slots,
                                                       const int64_t* __restrict__ old_deadline,
                                                       unsigned long long old_cap, CbTab tab) {
@@ -499,20 +439,11 @@ static __global__ void __launch_bounds__(BLOCK) k_cb_rebuild(const CbSlot* __res
     if (j >= old_cap) return;
     const CbSlot sl = old_slots[j];
     if (cb_state(sl.meta) != SLOT_LIVE) return;
-    unsigned long long s = cb_home(sl.id, tab.mask);
-    for (unsigned long long dist = 0; dist <= tab.mask; ++dist) {
-        uint32_t expected = 0;
-        if (__hip_atomic_compare_exchange_strong(&tab.slots[s].meta, &expected, cb_meta(SLOT_CLAIMED, 0, 0),
-                                                 __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-            tab.slots[s].id = sl.id;
-            tab.slots[s].handle = sl.handle;
-            tab.deadline[s] = old_deadline[j];
-            __hip_atomic_store(&tab.slots[s].meta, sl.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return;
-        }
-        s = (s + 1) & tab.mask;
-    }
-    atomicOr(&tab.ctr->err, CB_ERR_FULL);
+    const uint32_t d = rehash_place(CbSlots{tab.slots, tab.mask}, sl.id, sl.meta, [&](unsigned long long s) {
+        tab.slots[s].handle = sl.handle;
+        tab.deadline[s] = old_deadline[j];
+    });
+    if (d == NONE32) atomicOr(&tab.ctr->err, CB_ERR_FULL);
 }
 
 }  // namespace gd

@@ -2,7 +2,9 @@
 // (GrainDirectoryPartition.cs:304-326, GrainInfo :110-124), AddActivation (upsert), Merge's claims,
 // RemoveActivation (:335-363, Force), the ActivationDirectory's TryAdd / TryRemove, lookup and rehash.
 //
-// The protocol, in one place.
+// The protocol, in one place: the claim (claim_walk) and the rebuild's placement (rehash_place) are templates
+// over a table policy, DirSlots here for every table of 32-B slots (the directory, the activation directory, the
+// gateway's two) and CbSlots (gd_callbacks.h) for the callback table's 16-B slots.
 //
 // Slot states (gd_common.h, the meta's high half).  EMPTY ends a chain; TOMB keeps it going and is free
 // for reuse; LIVE holds a published entry.  A claim turns the key's first free slot -- its chain's first
@@ -103,27 +105,53 @@ __device__ __forceinline__ void live_delta(DevCounters* ctr, bool flag, bool rem
 }
 
 // ------------------------------------------------------------------ the claim
-// One item: find the key's slot or claim a free one (slot_of, is_new = the entry is this batch's).
-// vals / vt (vals nullable): an item whose silo is not valid is skipped (slot_of = NONE32): the IsValidSilo
-// check of AddSingleActivation / AddActivation (GrainDirectoryPartition.cs:279,310).
+// What differs between the tables that share the claim walk and the rehash (claim_walk, rehash_place): the
+// key and its home, the slot's words, the meta's layout.  This one is the 32-B Slot keyed by 24 B: the
+// directory, the activation directory and the gateway's two tables.  CbSlots (gd_callbacks.h) is the other.
+struct DirSlots {
+    using Key = gd_key;
+    Slot* slots;
+    unsigned long long mask;
+    __device__ __forceinline__ unsigned long long home(const gd_key& k) const {
+        return home_slot(uniform_hash(k.n0, k.n1, k.type_code_data), mask);
+    }
+    __device__ __forceinline__ uint32_t* meta(unsigned long long s) const { return &slots[s].meta; }
+    static __device__ __forceinline__ uint32_t state(uint32_t meta) { return slot_state(meta); }
+    static __device__ __forceinline__ uint32_t tag(uint32_t meta) { return slot_silo(meta); }
+    static __device__ __forceinline__ uint32_t claimed() { return make_meta(SLOT_CLAIMED, 0); }
+    static __device__ __forceinline__ uint32_t pending(uint32_t tag) { return make_meta(SLOT_PENDING, tag); }
+    // the key and a null value
+    __device__ __forceinline__ void put(unsigned long long s, const gd_key& k) const {
+        Slot& sl = slots[s];
+        sl.n0 = k.n0;
+        sl.n1 = k.n1;
+        sl.tcd = k.type_code_data;
+        sl.act = NONE32;
+    }
+    __device__ __forceinline__ bool holds(unsigned long long s, const gd_key& k) const {
+        const uint64_t k0 = slots[s].n0, k1 = slots[s].n1, k2 = slots[s].tcd;
+        return k0 == k.n0 && k1 == k.n1 && k2 == k.type_code_data;
+    }
+    static __device__ __forceinline__ bool same(const gd_key& a, const gd_key& b) {
+        return a.n0 == b.n0 && a.n1 == b.n1 && a.type_code_data == b.type_code_data;
+    }
+};
+
+// One item: find the key's slot or claim a free one (slot_of, is_new = the entry is this batch's).  Returns
+// whether this item made the claim.  err: the table's error word (bit 2: no free slot).
 // last is nullable: upsert and merge pass nullptr, because their word holds 1 + index (last wins), and an
 // election in ~i beside it would cost them a launch.
-__device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restrict__ keys, Slot* slots,
-                                               unsigned long long mask, DevCounters* ctr,
-                                               uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
-                                               const gd_val* __restrict__ vals, const TableArgs& vt, uint32_t* retry,
-                                               uint32_t& pdist, bool& reused, uint32_t tag,
-                                               uint32_t* __restrict__ last) {
-    if (vals && !tab_silo_valid(vt, vals[i].silo)) {
-        slot_of[i] = NONE32;
-        is_new[i] = 0;
-        return;
-    }
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
+template <typename P>
+__device__ __forceinline__ bool claim_walk(const P t, uint32_t i, const typename P::Key* __restrict__ keys,
+                                           uint32_t* err, uint32_t* __restrict__ slot_of,
+                                           uint8_t* __restrict__ is_new, uint32_t* retry, uint32_t& pdist, bool& reused,
+                                           uint32_t tag, uint32_t* __restrict__ last) {
+    const typename P::Key key = keys[i];
+    unsigned long long s = t.home(key);
     unsigned long long dist = 0;
     uint32_t res = NONE32;
     uint8_t fresh = 0;
+    bool claimed = false;
     // The key's first tombstone, reused when the chain does not hold the key (a directory under
     // continuous RemoveActivation / AddSingleActivation churn does not fill with tombstones until a
     // rehash).  Every item of one key meets the same first free slot, and a claim is a CAS, so a key is
@@ -135,34 +163,29 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
     unsigned long long tomb_s = ~0ull, tomb_dist = 0;
     uint32_t tomb_meta = 0;
     for (;;) {
-        uint32_t* meta_p = &slots[s].meta;
-        const uint32_t meta = __hip_atomic_load(meta_p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const uint32_t st = slot_state(meta);
+        const uint32_t meta = __hip_atomic_load(t.meta(s), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t st = P::state(meta);
         // the chain ends (an empty slot, or the whole table walked) without a copy of the key
-        const bool ends = st == SLOT_EMPTY || dist > mask;
+        const bool ends = st == SLOT_EMPTY || dist > t.mask;
         if (ends && st != SLOT_EMPTY && tomb_s == ~0ull) {
-            atomicOr(&ctr->err, 2u);                         // no free slot: the table is full
+            atomicOr(err, 2u);                               // no free slot: the table is full
             break;
         }
         bool won = false;
         const bool tomb = tomb_s != ~0ull;
-        const unsigned long long t = tomb ? tomb_s : s, d = tomb ? tomb_dist : dist;
+        const unsigned long long c = tomb ? tomb_s : s, d = tomb ? tomb_dist : dist;
         if (ends) {
-            // claim slot t for the key: the claimer's index in the slot's election word (readable by this
+            // claim slot c for the key: the claimer's index in the slot's election word (readable by this
             // launch's walks), the key, then PENDING with this launch's tag (read as unpublished by this
             // launch's other items; published to later launches by the kernel boundary)
             uint32_t expected = tomb ? tomb_meta : meta;
-            uint32_t* mp = &slots[t].meta;
-            won = __hip_atomic_compare_exchange_strong(mp, &expected, make_meta(SLOT_CLAIMED, 0), __ATOMIC_RELAXED,
-                                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t* mp = t.meta(c);
+            won = __hip_atomic_compare_exchange_strong(mp, &expected, P::claimed(), __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                       __HIP_MEMORY_SCOPE_AGENT);
             if (won) {
-                if (last) atomicMax(&last[t], ~i);
-                Slot& sl = slots[t];
-                sl.n0 = n0;
-                sl.n1 = n1;
-                sl.tcd = tcd;
-                sl.act = NONE32;
-                __hip_atomic_store(mp, make_meta(SLOT_PENDING, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (last) atomicMax(&last[c], ~i);
+                t.put(c, key);
+                __hip_atomic_store(mp, P::pending(tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
         // The winner's writes above stay inside the loop: the wave's losers of the same slot read the election
@@ -178,18 +201,19 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
         if (won) {
             pdist = (uint32_t)d;                             // max_probe: claim_counters
             reused = tomb;                                   // tomb - 1: claim_counters
-            res = (uint32_t)t;
+            res = (uint32_t)c;
             fresh = 1;
+            claimed = true;
             break;
         }
         if (ends) {
-            // lost slot t: walk on from it (an empty slot that was lost is read again as it is)
-            s = t;
+            // lost slot c: walk on from it (an empty slot that was lost is read again as it is)
+            s = c;
             dist = d;
             tomb_s = ~0ull;
             continue;
         }
-        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && slot_silo(meta) == tag);
+        const bool unpublished = st == SLOT_CLAIMED || (st == SLOT_PENDING && P::tag(meta) == tag);
         if (unpublished) {
             // claimed in this launch: its key is not published to this launch, but its claimer is (the slot's
             // election word, written right after the claim): the key's twin -- join it -- or another key's
@@ -201,8 +225,7 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
                 atomicAdd(retry, 1u);
                 break;
             }
-            const gd_key& c = keys[~w];
-            if (c.n0 == n0 && c.n1 == n1 && c.type_code_data == tcd) {
+            if (P::same(keys[~w], key)) {
                 res = (uint32_t)s;
                 fresh = 1;
                 break;
@@ -214,22 +237,59 @@ __device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restr
             tomb_dist = dist;
         }
         if (!unpublished && (st == SLOT_LIVE || st == SLOT_PENDING)) {   // a key published before this launch
-            const uint64_t k0 = slots[s].n0, k1 = slots[s].n1, k2 = slots[s].tcd;
-            if (k0 == n0 && k1 == n1 && k2 == tcd) {
+            if (t.holds(s, key)) {
                 res = (uint32_t)s;
                 fresh = (st == SLOT_PENDING) ? 1 : 0;
                 break;
             }
         }
-        s = (s + 1) & mask;
+        s = (s + 1) & t.mask;
         ++dist;
     }
     slot_of[i] = res;
     is_new[i] = fresh;
+    return claimed;
+}
+
+// The walk over a 32-B-slot table, behind the IsValidSilo check of AddSingleActivation / AddActivation
+// (GrainDirectoryPartition.cs:279,310): vals / vt (vals nullable), an item whose silo is not valid is skipped
+// (slot_of = NONE32).
+__device__ __forceinline__ void reg_claim_item(uint32_t i, const gd_key* __restrict__ keys, Slot* slots,
+                                               unsigned long long mask, DevCounters* ctr,
+                                               uint32_t* __restrict__ slot_of, uint8_t* __restrict__ is_new,
+                                               const gd_val* __restrict__ vals, const TableArgs& vt, uint32_t* retry,
+                                               uint32_t& pdist, bool& reused, uint32_t tag,
+                                               uint32_t* __restrict__ last) {
+    if (vals && !tab_silo_valid(vt, vals[i].silo)) {
+        slot_of[i] = NONE32;
+        is_new[i] = 0;
+        return;
+    }
+    (void)claim_walk(DirSlots{slots, mask}, i, keys, &ctr->err, slot_of, is_new, retry, pdist, reused, tag, last);
+}
+
+// A known-distinct live entry into a zeroed table (the rebuilds: no key is compared): the first EMPTY slot from
+// the key's home on, claimed by CAS; payload(s) stores what put() left null; then the meta.  Returns the probe
+// distance, or NONE32 when the table has no empty slot.
+template <typename P, typename F>
+__device__ __forceinline__ uint32_t rehash_place(const P t, const typename P::Key& key, uint32_t meta, F payload) {
+    unsigned long long s = t.home(key);
+    for (unsigned long long dist = 0; dist <= t.mask; ++dist) {
+        uint32_t expected = 0;                               // EMPTY
+        if (__hip_atomic_compare_exchange_strong(t.meta(s), &expected, P::claimed(), __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT)) {
+            t.put(s, key);
+            payload(s);
+            __hip_atomic_store(t.meta(s), meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return (uint32_t)dist;
+        }
+        s = (s + 1) & t.mask;
+    }
+    return NONE32;
 }
 
 // A read-back-driven claim pass.  pass 0: every item; later passes: the items the previous one deferred.
-// last: see reg_claim_item; set, an item that ends with a new entry (claimed it, or found it PENDING)
+// last: see claim_walk; set, an item that ends with a new entry (claimed it, or found it PENDING)
 // elects itself.
 static __global__ void __launch_bounds__(BLOCK) k_reg_claim(const gd_key* __restrict__ keys, uint32_t n, Slot* slots,
                                                      unsigned long long mask, DevCounters* ctr,
@@ -528,21 +588,9 @@ __device__ __forceinline__ void unreg_find_elect_item(uint32_t i, const gd_key* 
                                                       const uint32_t* __restrict__ acts, const Slot* slots,
                                                       unsigned long long mask, const DevCounters* ctr,
                                                       uint32_t* __restrict__ slot_of, uint32_t* __restrict__ last) {
-    const uint64_t n0 = keys[i].n0, n1 = keys[i].n1, tcd = keys[i].type_code_data;
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
-    uint32_t res = NONE32;
-    for (uint32_t p = 0; p <= ctr->max_probe; ++p) {
-        const uint4* q = reinterpret_cast<const uint4*>(slots + s);
-        const uint4 a = q[0], b = q[1];
-        const uint32_t st = slot_state(b.w);
-        if (st == SLOT_EMPTY) break;
-        if (st == SLOT_LIVE && ((uint64_t)a.x | ((uint64_t)a.y << 32)) == n0 &&
-            ((uint64_t)a.z | ((uint64_t)a.w << 32)) == n1 && ((uint64_t)b.x | ((uint64_t)b.y << 32)) == tcd) {
-            if (b.z == acts[i]) res = (uint32_t)s;
-            break;
-        }
-        s = (s + 1) & mask;
-    }
+    uint4 b;
+    uint32_t res = find_slot(slots, mask, ctr->max_probe, keys[i].n0, keys[i].n1, keys[i].type_code_data, b);
+    if (res != NONE32 && b.z != acts[i]) res = NONE32;     // the grain's entry holds another activation
     slot_of[i] = res;
     if (res != NONE32) atomicMax(&last[res], ~i);
 }
@@ -597,24 +645,14 @@ static __global__ void __launch_bounds__(BLOCK) k_rehash(const Slot* __restrict_
     bool placed = false;
     const Slot sl = j < old_cap ? old_slots[j] : Slot{};
     if (j < old_cap && slot_state(sl.meta) == SLOT_LIVE) {
-        unsigned long long s = home_slot(uniform_hash(sl.n0, sl.n1, sl.tcd), mask);
-        for (uint32_t dist = 0; dist <= mask; ++dist) {
-            uint32_t expected = make_meta(SLOT_EMPTY, 0);
-            if (__hip_atomic_compare_exchange_strong(&slots[s].meta, &expected, make_meta(SLOT_CLAIMED, 0),
-                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                slots[s].n0 = sl.n0;
-                slots[s].n1 = sl.n1;
-                slots[s].tcd = sl.tcd;
-                slots[s].act = sl.act;
-                if (vtag) vtag[s] = old_vtag[j];
-                __hip_atomic_store(&slots[s].meta, sl.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pd = dist;
-                placed = true;
-                break;
-            }
-            s = (s + 1) & mask;
-        }
-        if (!placed) atomicOr(&ctr->err, 2u);
+        const DirSlots t{slots, mask};
+        const uint32_t d = rehash_place(t, gd_key{sl.n0, sl.n1, sl.tcd}, sl.meta, [&](unsigned long long s) {
+            slots[s].act = sl.act;
+            if (vtag) vtag[s] = old_vtag[j];
+        });
+        placed = d != NONE32;
+        if (placed) pd = d;
+        else atomicOr(&ctr->err, 2u);
     }
     // one max_probe / live update a wave (one an entry queued 10^6 same-address atomics at cfg 2)
     claim_counters(ctr, pd, false);

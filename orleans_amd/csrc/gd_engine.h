@@ -714,4 +714,93 @@ struct HostStage {
     }
 };
 
+// ---- the stages that keep a table of their own (the callback table, the gateway's two)
+// The claim passes of a batch (gd_dirbatch.h) over the `passes` words of `retry`, zeroed here: run(p, gate,
+// word) launches pass p, which counts the items it defers into `word` and, with a gate, runs only if the gate
+// word is not zero.  Pass 0, then (sync_passes, the host forms) one pass after each read-back of a count that is
+// not zero; else passes - 1 gated ones, *unsettled = the last one's word for the caller's flag (null otherwise).
+template <typename F>
+int claim_pass_driver(gd_handle* h, uint32_t* retry, uint32_t passes, bool sync_passes, const char* call,
+                      const uint32_t** unsettled, F run) {
+    *unsettled = nullptr;
+    HIP_TRY(h, hipMemsetAsync(retry, 0, sizeof(uint32_t) * passes, h->stream));
+    GD_TRY(run(0u, (const uint32_t*)nullptr, &retry[0]));
+    if (sync_passes) {
+        for (uint32_t p = 1;; ++p) {
+            uint32_t deferred = 0;
+            GD_TRY(read_back(h, &retry[(p - 1) % passes], &deferred, 1));
+            if (!deferred) return GD_OK;
+            if (p > 4096) return set_err(h, GD_ETIMEOUT, "%s: the claims did not settle", call);
+            HIP_TRY(h, hipMemsetAsync(&retry[p % passes], 0, 4, h->stream));
+            GD_TRY(run(p, (const uint32_t*)nullptr, &retry[p % passes]));
+        }
+    }
+    for (uint32_t p = 1; p < passes; ++p) GD_TRY(run(p, (const uint32_t*)&retry[p - 1], &retry[p]));
+    *unsettled = &retry[passes - 1];
+    return GD_OK;
+}
+
+// Room for `incoming` new entries at load <= 0.75, counting tombstones.  Without a read-back while the bound kept
+// on the host (used_ub: every add since the last read-back counted as a new slot) allows it; else pull(live,
+// tomb) reads the counters and, if need be, rebuild(cap, live) rebuilds the table: at the same capacity while the
+// live entries fill at most half of it, else at double (and on until the batch fits).
+template <typename Pull, typename Rebuild>
+int table_reserve(gd_handle* h, uint64_t& used_ub, unsigned long long cap, uint64_t incoming, const char* call,
+                  Pull pull, Rebuild rebuild) {
+    if ((used_ub + incoming) * 4 <= cap * 3) {
+        used_ub += incoming;
+        return GD_OK;
+    }
+    GD_TRY(check_not_capturing(h, call));
+    uint64_t live = 0, tomb = 0;
+    GD_TRY(pull(live, tomb));
+    if ((live + tomb + incoming) * 4 > cap * 3) {
+        if (live * 2 > cap) cap *= 2;
+        while ((live + incoming) * 4 > cap * 3) cap *= 2;
+        GD_TRY(rebuild(cap, live));
+        tomb = 0;
+    }
+    used_ub = live + tomb + incoming;
+    return GD_OK;
+}
+
+// A zeroed table of `cap` slots of slot_bytes, the values beside them (side_bytes a slot) and two election
+// words a slot: all three, or none and GD_EFULL.
+inline int table_alloc(gd_handle* h, const char* what, unsigned long long cap, size_t slot_bytes, size_t side_bytes,
+                       DevBuf& slots, DevBuf& side, DevBuf& last) {
+    int r = ensure(h, slots, (size_t)cap * slot_bytes);
+    if (r == GD_OK) r = ensure(h, side, (size_t)cap * side_bytes);
+    if (r == GD_OK) r = ensure(h, last, (size_t)cap * 8);
+    if (r != GD_OK) {
+        free_buf(slots);
+        free_buf(side);
+        free_buf(last);
+        return set_err(h, GD_EFULL, "%s table: no memory for %llu slots", what, cap);
+    }
+    HIP_TRY(h, hipMemsetAsync(slots.p, 0, (size_t)cap * slot_bytes, h->stream));
+    HIP_TRY(h, hipMemsetAsync(last.p, 0, (size_t)cap * 8, h->stream));
+    return GD_OK;
+}
+
+// The end of a rebuild: once the stream is done with the old table, the new buffers take its place.
+inline int table_swap(gd_handle* h, DevBuf* const (&old)[3], const DevBuf (&fresh)[3], unsigned long long& cap,
+                      unsigned long long new_cap) {
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < 3; ++k) {
+        free_buf(*old[k]);
+        *old[k] = fresh[k];
+    }
+    cap = new_cap;
+    return GD_OK;
+}
+
+// Device error bits just read back are cleared (they are reported once); ERR_UNSETTLED among them: votes may be
+// left in the election words (two a slot), which are zeroed.
+inline int table_err_clear(gd_handle* h, uint32_t* d_err, uint32_t err, const DevBuf& last, unsigned long long cap) {
+    HIP_TRY(h, hipMemsetAsync(d_err, 0, 4, h->stream));
+    if (err & ERR_UNSETTLED) HIP_TRY(h, hipMemsetAsync(last.p, 0, (size_t)cap * 8, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return GD_OK;
+}
+
 }  // namespace gdx

@@ -5,13 +5,13 @@
 // GatewayAcceptor.HandleMessage (GatewayAcceptor.cs:88-141) for a batch.
 //
 // The tables.  Both are keyed by a 24-B GrainId of category Client, so both are the directory's 32-B Slot
-// (gd_common.h) with its home (home_slot of the Jenkins hash), its states, its claim and its election words
-// (gd_dirbatch.h: reg_claim_item is called as it is; nothing of gd_dirbatch.h is changed), and what does not fit
-// the slot lies beside it, slot for slot:
+// (gd_common.h) with its home (home_slot of the Jenkins hash), its states, its claim and its election words:
+// gd_dirbatch.h's claim_walk and rehash_place over DirSlots, the directory's own policy (reg_claim_item with no
+// IsValidSilo values).  What does not fit the slot lies beside it, slot for slot:
 //   clients   act = the ClientState handle, meta's low 16 bits = GatewaySenderNumber (< 1,024);
 //             GwClient {DisconnectedSince i64, PendingToSend.Count u32, connected u32}: one 16-B load
 //   routes    act = the gateway silo index (GD_NO_SILO allowed); the recorded tick, i64
-// A lookup (gw_find) walks from the home with whole-slot loads (two 16-B loads a slot) for at most
+// A lookup (find_slot, gd_probe.h) walks from the home with whole-slot loads (two 16-B loads a slot) for at most
 // DevCounters::max_probe + 1 slots; EMPTY ends a chain, TOMB keeps it going.  Two election words a slot, zero
 // between calls: word 0 in ~i (first wins; it also names a fresh claim's claimer to the launch's other items),
 // word 1 in 1 + i (last wins).
@@ -55,7 +55,7 @@ namespace gd {
 
 constexpr uint32_t CAT_CLIENT = 4;               // UniqueKey.Category.Client (UniqueKey.cs:23)
 constexpr uint32_t GW_PASSES = REG_PASSES;       // claim passes of the device forms
-constexpr uint32_t GW_ERR_FULL = 2u;             // DevCounters::err (reg_claim_item's bit)
+constexpr uint32_t GW_ERR_FULL = 2u;             // DevCounters::err (claim_walk's bit)
 
 struct alignas(16) GwClient {
     int64_t since;          // DisconnectedSince in ticks; INT64_MAX while connected
@@ -81,24 +81,6 @@ __device__ __forceinline__ uint32_t* gw_win(const GwTab& t) { return t.last + (t
 GD_HD uint32_t gw_cat(uint64_t tcd) { return (uint32_t)(tcd >> 56); }
 // GrainId.IsClient (GrainId.cs:23): Client or GeoClient
 GD_HD bool gw_is_client(uint32_t cat) { return cat == CAT_CLIENT || cat == CAT_GEO_CLIENT; }
-
-// The live slot of the key, or NONE32; b = the slot's second half {tcd, act, meta}.
-__device__ __forceinline__ uint32_t gw_find(const Slot* __restrict__ slots, unsigned long long mask,
-                                            uint32_t max_probe, uint64_t n0, uint64_t n1, uint64_t tcd, uint4& b) {
-    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
-    for (uint32_t p = 0; p <= max_probe; ++p) {
-        const uint4* q = reinterpret_cast<const uint4*>(slots + s);
-        const uint4 a = q[0];
-        b = q[1];
-        const uint32_t st = slot_state(b.w);
-        if (st == SLOT_EMPTY) break;
-        if (st == SLOT_LIVE && ((uint64_t)a.x | ((uint64_t)a.y << 32)) == n0 &&
-            ((uint64_t)a.z | ((uint64_t)a.w << 32)) == n1 && ((uint64_t)b.x | ((uint64_t)b.y << 32)) == tcd)
-            return (uint32_t)s;
-        s = (s + 1) & mask;
-    }
-    return NONE32;
-}
 
 // ------------------------------------------------------------------ claims (open, the route upsert)
 // A claim pass.  init (open's pass 0): every key of category Client runs, the others get NONE32; else the items
@@ -235,7 +217,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_find(const gd_key* __restri
     const uint64_t tcd = keys[i].type_code_data;
     uint32_t s = NONE32;
     uint4 b;
-    if (gw_cat(tcd) == CAT_CLIENT) s = gw_find(t.slots, t.mask, t.ctr->max_probe, keys[i].n0, keys[i].n1, tcd, b);
+    if (gw_cat(tcd) == CAT_CLIENT) s = find_slot(t.slots, t.mask, t.ctr->max_probe, keys[i].n0, keys[i].n1, tcd, b);
     slot_of[i] = s;
     if (vote && s != NONE32) atomicMax(&vote[s], ~i);
 }
@@ -332,7 +314,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_lookup(const gd_key* __rest
     const bool client = gw_cat(tcd) == CAT_CLIENT;
     if (o.handle || o.sender || o.connected || o.since || o.pending || o.found) {
         uint4 b;
-        const uint32_t s = client ? gw_find(ct.slots, ct.mask, ct.ctr->max_probe, n0, n1, tcd, b) : NONE32;
+        const uint32_t s = client ? find_slot(ct.slots, ct.mask, ct.ctr->max_probe, n0, n1, tcd, b) : NONE32;
         GwClient c{0, 0u, 0u};
         if (s != NONE32) c = cside[s];
         if (o.handle) o.handle[i] = s != NONE32 ? b.z : NONE32;
@@ -344,7 +326,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_lookup(const gd_key* __rest
     }
     if (o.route_silo || o.route_time || o.route_found) {
         uint4 b;
-        const uint32_t s = client ? gw_find(rt.slots, rt.mask, rt.ctr->max_probe, n0, n1, tcd, b) : NONE32;
+        const uint32_t s = client ? find_slot(rt.slots, rt.mask, rt.ctr->max_probe, n0, n1, tcd, b) : NONE32;
         if (o.route_silo) o.route_silo[i] = s != NONE32 ? b.z : NONE32;
         if (o.route_time) o.route_time[i] = s != NONE32 ? rtime[s] : 0;
         if (o.route_found) o.route_found[i] = s != NONE32 ? 1 : 0;
@@ -382,7 +364,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_deliver(const gd_key* __res
             st = GD_GW_GEO_CLIENT;
         } else if (cat == CAT_CLIENT) {
             uint4 b;
-            const uint32_t s = gw_find(ct.slots, ct.mask, ct.ctr->max_probe, target[i].n0, target[i].n1, tcd, b);
+            const uint32_t s = find_slot(ct.slots, ct.mask, ct.ctr->max_probe, target[i].n0, target[i].n1, tcd, b);
             if (s != NONE32) {
                 handle = b.z;
                 sender = slot_silo(b.w);
@@ -500,7 +482,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_ingress(const gd_key* __res
             st = GD_GWIN_GEO_CLIENT;
         } else if (both) {
             uint4 b;
-            const uint32_t s = gw_find(rt.slots, rt.mask, rt.ctr->max_probe, target[i].n0, target[i].n1, tcd, b);
+            const uint32_t s = find_slot(rt.slots, rt.mask, rt.ctr->max_probe, target[i].n0, target[i].n1, tcd, b);
             if (s != NONE32 && b.z != NONE32) {              // a route with no gateway reroutes
                 st = GD_GWIN_DIRECT;
                 silo = b.z;
@@ -529,7 +511,7 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_ingress_emit(const gd_key* 
 
 // ------------------------------------------------------------------ rebuild
 // Every live entry of the old table, with its value, into the new, zeroed one (k_rehash with the value beside
-// the slot; keys are distinct, so a claimer compares none).
+// the slot).
 template <typename T>
 static __global__ void __launch_bounds__(BLOCK) k_gw_rehash(const Slot* __restrict__ old_slots,
                                                      const T* __restrict__ old_side, unsigned long long old_cap,
@@ -540,24 +522,14 @@ static __global__ void __launch_bounds__(BLOCK) k_gw_rehash(const Slot* __restri
     bool placed = false;
     const Slot sl = j < old_cap ? old_slots[j] : Slot{};
     if (j < old_cap && slot_state(sl.meta) == SLOT_LIVE) {
-        unsigned long long s = home_slot(uniform_hash(sl.n0, sl.n1, sl.tcd), mask);
-        for (unsigned long long dist = 0; dist <= mask; ++dist) {
-            uint32_t expected = make_meta(SLOT_EMPTY, 0);
-            if (__hip_atomic_compare_exchange_strong(&slots[s].meta, &expected, make_meta(SLOT_CLAIMED, 0),
-                                                     __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                slots[s].n0 = sl.n0;
-                slots[s].n1 = sl.n1;
-                slots[s].tcd = sl.tcd;
-                slots[s].act = sl.act;
-                side[s] = old_side[j];
-                __hip_atomic_store(&slots[s].meta, sl.meta, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                pd = (uint32_t)dist;
-                placed = true;
-                break;
-            }
-            s = (s + 1) & mask;
-        }
-        if (!placed) atomicOr(&ctr->err, GW_ERR_FULL);
+        const DirSlots t{slots, mask};
+        const uint32_t d = rehash_place(t, gd_key{sl.n0, sl.n1, sl.tcd}, sl.meta, [&](unsigned long long s) {
+            slots[s].act = sl.act;
+            side[s] = old_side[j];
+        });
+        placed = d != NONE32;
+        if (placed) pd = d;
+        else atomicOr(&ctr->err, GW_ERR_FULL);
     }
     claim_counters(ctr, pd, false);
     live_delta(ctr, placed, false);

@@ -244,4 +244,23 @@ __device__ __forceinline__ bool probe(const Slot* slots, unsigned long long mask
     return false;
 }
 
+// probe() for the batches that go on to change the entry: the slot of the key's live entry, or NONE32;
+// b = the last slot read's second half {tcd, act, meta}, the entry's own on a hit.
+__device__ __forceinline__ uint32_t find_slot(const Slot* __restrict__ slots, unsigned long long mask,
+                                              uint32_t max_probe, uint64_t n0, uint64_t n1, uint64_t tcd, uint4& b) {
+    unsigned long long s = home_slot(uniform_hash(n0, n1, tcd), mask);
+    for (uint32_t p = 0; p <= max_probe; ++p) {
+        const uint4* q = reinterpret_cast<const uint4*>(slots + s);
+        const uint4 a = q[0];
+        b = q[1];
+        const uint32_t st = slot_state(b.w);
+        if (st == SLOT_EMPTY) break;
+        if (st == SLOT_LIVE && ((uint64_t)a.x | ((uint64_t)a.y << 32)) == n0 &&
+            ((uint64_t)a.z | ((uint64_t)a.w << 32)) == n1 && ((uint64_t)b.x | ((uint64_t)b.y << 32)) == tcd)
+            return (uint32_t)s;
+        s = (s + 1) & mask;
+    }
+    return NONE32;
+}
+
 }  // namespace gd

@@ -168,6 +168,66 @@ def test_small_table_chains_wrap(eng):
     m.add(absent[:10], np.arange(10, dtype=np.uint32), np.zeros(10, np.int64))
 
 
+def _tombstoned_chain_add(e, device):
+    """28 entries homed in the last three groups of a 64-slot table (the engine's minimum): one chain over slots
+    52 .. 63, 0 .. 15.  Every other one fires, which leaves 14 tombstones inside it.  Then one batch of 20 items adds
+    15 new ids, every third of them twice; 28 + 20 = 48 is all the 0.75 load rule admits without a rebuild, which
+    would sweep the tombstones under test away.  The new ids are homed in the chain's first group, so every
+    tombstone lies ahead of every one of them and the counts afterwards do not depend on which lane claims first:
+    14 tombstones reused, one EMPTY slot taken, 29 live, no tombstone, 64 slots.  device: the batch goes through
+    gd_callbacks_add_device (the gated passes), else gd_callbacks_add (read-back-driven ones).  Returns the
+    batch's `added` and what a lookup of its ids finds."""
+    import torch
+    m = Mirror(e, 64)
+    pool = np.arange(1, 4000, dtype=np.int64)
+    g = np.array([home_group(i, 64) for i in pool])
+    old = pool[g >= 13][:28]
+    assert m.add(old, np.arange(28, dtype=np.uint32) + 100, np.arange(28, dtype=np.int64)) == 64
+    m.respond(old[::2])
+    new = np.setdiff1d(pool[g == 13], old)[:15]
+    assert len(new) == 15
+    batch = np.r_[new, new[2::3]]
+    np.random.default_rng(3).shuffle(batch)                  # twins at any distance, either order
+    handles, dl = np.arange(20, dtype=np.uint32) + 500, np.arange(20, dtype=np.int64) + 7
+    want = m.t.add(batch, handles, dl)
+    assert want.sum() == 15
+    m.seen |= set(int(x) for x in batch)
+    if device:
+        dev = torch.device("cuda:0")
+        d_ids, d_h, d_dl = (torch.from_numpy(a.view(np.uint8).copy()).to(dev) for a in (batch, handles, dl))
+        d_added = torch.zeros(20, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        e.callbacks_add_device(d_ids.data_ptr(), d_h.data_ptr(), d_dl.data_ptr(), 20, d_added.data_ptr())
+        e.synchronize()
+        added = d_added.cpu().numpy().copy()
+    else:
+        added = e.callbacks_add(batch, handles, dl)
+    _eq((added,), (want,), ("added",))                       # the first item of each id, not its repeats
+    # the next synchronising calls report no GD_ETIMEOUT (they raise on one); survivors, fired and new ids as the model
+    assert m.verify() == 64 and e.callbacks_count() == (29, 64)
+    # no tombstone is left: 19 more adds fit the host's bound, 29 + 0 + 19 <= 48, without the rebuild that one
+    # leftover tombstone would bring
+    e.set_kernel_timing(True)
+    e.kernel_times_reset()
+    more = pool[g == 5][:19]
+    m.add(more, np.zeros(19, np.uint32), np.zeros(19, np.int64))
+    times = e.kernel_times()
+    e.set_kernel_timing(False)
+    assert "k_cb_claim" in times and "k_cb_rebuild" not in times
+    return (added,) + tuple(e.callbacks_lookup(batch))
+
+
+def test_tombstoned_wrapped_chain_device_form(eng):
+    _tombstoned_chain_add(eng, device=True)
+
+
+def test_tombstoned_wrapped_chain_host_form_matches_device(eng):
+    host = _tombstoned_chain_add(eng, device=False)
+    eng.callbacks_clear()
+    dev = _tombstoned_chain_add(eng, device=True)
+    _eq(host, dev, ("added", "handle", "resend", "silo", "found"))
+
+
 # ---- respond ----------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("n", EDGES)
