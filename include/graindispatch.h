@@ -79,7 +79,8 @@ extern "C" {
 
 #define GD_ROUTE_MULTI_ACT      7 /* the grain has several activations (GrainInfo.Instances.Count >= 2,
                                      e.g. StatelessWorker): RandomPlacementDirector picks one in C#
-                                     (RandomPlacementDirector.cs:33-53); out_silo = directory owner */
+                                     (RandomPlacementDirector.cs:33-53); out_silo = directory owner.
+                                     A StatelessWorker class's own messages: gd_workers_select* */
 
 #define GD_NO_ACTIVATION 0xFFFFFFFFu
 #define GD_ACT_MULTI     0xFFFFFFFEu   /* gd_val.act of a multi-activation grain (gd_dir_upsert)   */
@@ -1082,7 +1083,7 @@ int gd_route_send(gd_handle* h, const gd_key* keys, uint32_t n, const uint8_t* c
  *   GD_PLACE_GIVEN  given_silo[i]: RandomPlacementDirector and ActivationCountPlacementDirector.cs:89-122
  *                   draw SafeRandom, so C# makes the choice and the library applies it (no given array:
  *                   skipped)
- * StatelessWorker grains (many activations, always local) are not placed here.
+ * StatelessWorker grains (many activations, always local) are addressed by gd_workers_select*.
  *
  * Candidates: the messages that end the route GD_ROUTE_MISS and whose UniqueKey category is Grain (a Client
  * target is never placed, PlacementDirectorsManager.cs:85-93,108-109).  Every other message -- KeyExt grains,
@@ -1763,6 +1764,95 @@ int gd_gateway_ingress_device(gd_handle* h, const gd_key* d_target_grain, const 
 int gd_gateway_ingress(gd_handle* h, const gd_key* target_grain, const gd_key* sending_grain, const uint8_t* direction,
                        const int64_t* ttl, uint32_t n, int overloaded, uint8_t* out_status, uint32_t* out_silo,
                        uint32_t* route_idx, uint32_t* n_route, gd_key* route_keys);
+
+/* ---- stateless workers: worker sets, pick, grow, spread --------------------------------
+ * A message to a grain class whose strategy is StatelessWorkerPlacement is addressed by
+ * StatelessWorkerDirector.SelectActivationCore (Placement/StatelessWorkerDirector.cs:31-62): FindTargets copies the
+ * grain's local activations under a lock (ActivationDirectory.cs:150-158), the first Valid and inactive one
+ * (ActivationData.IsInactive, ActivationData.cs:689-703) takes the message (:46-53), else a new local activation is
+ * made while fewer than MaxLocal exist (:26-29,61), else a random one is drawn (:55-59).  gd_workers_select* does
+ * this for a batch over worker sets kept on the device, and its d_ctx feeds gd_turns_device directly.
+ *
+ * State: one table per handle, GrainId -> set = {count, max_local, the ctx list in List<ActivationData> order, at
+ * most slot_capacity entries}.  gd_workers_configure(capacity = sets expected, slot_capacity, default_max_local):
+ * 1 <= slot_capacity <= GD_WK_MAX_SLOT_CAPACITY and 1 <= default_max_local <= slot_capacity, else GD_EINVAL;
+ * called again it may raise the capacity, and change slot_capacity only while no set exists.  The batch calls
+ * return GD_ESTATE before it.  The table grows on its own.  The contexts of one set are distinct (the caller's
+ * promise; 0xFFFFFFFF is no context).
+ *
+ * The batch model (a choice: one legal interleaving of the reference, not something it guarantees).  Messages are
+ * addressed in batch order, and each is delivered (Dispatcher.ReceiveRequest) before the next is addressed.  So a
+ * worker picked while inactive is executing for the rest of the batch, a worker the batch creates is in state
+ * Create (not Valid) for the rest of the batch, and nothing completes inside the batch.  Per set at the batch
+ * start: L[0..c) its list, m its MaxLocal, I the entries of L, in list order, with ctx < n_ctx, state
+ * GD_CTX_VALID, (int32)num_running <= 0 and an empty waiting list (d_wait_offsets: gd_wait_list's offsets, NULL =
+ * all empty); a = |I|, room = max(0, m - c), C = c + room.  The message whose stable rank among the batch's
+ * messages of that set is k gets d_pick:
+ *   GD_WK_IDLE    k < a: d_ctx = I[k].
+ *   GD_WK_NEW     a <= k < a + room: d_ctx = ctx_base + g, g = the message's rank among the call's NEW messages
+ *                 in batch order (dense); the library appends L[c + (k - a)] = d_ctx.
+ *   GD_WK_RANDOM  otherwise: d_ctx = L'[r] of the final list L' (length C); r = 0 when C == 1 (the draw is not
+ *                 read), else (int)(((double)d_draw[i] * (1.0 / 2147483647.0)) * (double)C): Random.Next(C) on
+ *                 the internal sample C# got from random.Next() for this message.
+ *   GD_WK_HELD    a RANDOM message with d_draw NULL or d_draw[i] >= 0x7FFFFFFF: left to C#, its rank consumed;
+ *                 also a message whose max_local exceeds slot_capacity (it takes no part and creates nothing).
+ *   GD_WK_NONE    the key's UniqueKey category is not Grain (the reference throws for clients, :33-34).
+ * HELD and NONE give d_ctx 0xFFFFFFFF.  A message of a grain with no set creates it (c = 0) with m = its
+ * d_max_local entry (int32; <= 0, or the array NULL = default_max_local); the first such message decides.
+ * d_new_idx[0 .. n_new) lists the NEW messages in batch order (optional, with n_new: both or neither, else
+ * GD_EINVAL); n_new is a device word in the device form.  ctx_base + n past GD_ACT_MULTI is GD_EINVAL (n_new <= n
+ * is what the host knows before the batch runs).  With n_ctx > 0 the two context arrays are required.
+ *
+ * gd_workers_add*: RecordNewTarget (ActivationDirectory.cs:86-93) for a batch, appended in batch order, several
+ * of one grain included; a grain with no set gets one with the item's max_local.  out_status: GD_WK_ADDED,
+ * GD_WK_FULL (the list is at slot_capacity, or max_local > slot_capacity), GD_WK_NOT_GRAIN.
+ * gd_workers_remove*: RemoveTarget's list.Remove (:116-147) per (grain, ctx) pair in batch order: the first
+ * occurrence goes, the order of the rest is kept, a set left empty is removed; out_removed = 1 / 0.
+ * gd_workers_lookup*: per key count, max_local and the list (n * slot_capacity words, the unused tail
+ * 0xFFFFFFFF; each output optional); a grain with no set reads 0, 0, empty.
+ *
+ * The device forms are enqueue-only on the handle's stream while the host's bound (one new set a message since
+ * the last read-back) leaves the table under load 0.75; past it a batch that may create sets reads its count of
+ * set-less messages back, and grows the table when they need the room.  select and add run 12 gated claim
+ * passes; a batch that did not settle in them is reported as GD_ETIMEOUT by the next synchronising gd_workers_*
+ * call (its unsettled messages are HELD / FULL).  All three batch calls reuse the bucketing, so they return
+ * GD_ESTATE inside a hipGraph capture, as gd_turns_device does, with nothing launched.  The host forms are
+ * synchronous.  n <= 2^31; n == 0 is valid.
+ *
+ * Left to C#: the registration-time overshoot check and its PickRandom (Catalog.cs:1284-1293), re-routing of
+ * queued messages when a worker deactivates, and the RNG itself (SafeRandom: the host passes what Next() gave). */
+#define GD_WK_MAX_SLOT_CAPACITY 1024
+#define GD_WK_NONE   0
+#define GD_WK_IDLE   1
+#define GD_WK_NEW    2
+#define GD_WK_RANDOM 3
+#define GD_WK_HELD   4
+#define GD_WK_NOT_GRAIN 0            /* gd_workers_add's out_status */
+#define GD_WK_ADDED     1
+#define GD_WK_FULL      2
+int gd_workers_configure(gd_handle* h, uint64_t capacity, uint32_t slot_capacity, uint32_t default_max_local);
+int gd_workers_clear(gd_handle* h);
+int gd_workers_count(gd_handle* h, uint64_t* out_sets, uint64_t* out_capacity);
+int gd_workers_add_device(gd_handle* h, const gd_key* d_grains, const uint32_t* d_ctx, const int32_t* d_max_local,
+                          uint32_t n, uint8_t* d_out_status);
+int gd_workers_add(gd_handle* h, const gd_key* grains, const uint32_t* ctx, const int32_t* max_local, uint32_t n,
+                   uint8_t* out_status);
+int gd_workers_remove_device(gd_handle* h, const gd_key* d_grains, const uint32_t* d_ctx, uint32_t n,
+                             uint8_t* d_out_removed);
+int gd_workers_remove(gd_handle* h, const gd_key* grains, const uint32_t* ctx, uint32_t n, uint8_t* out_removed);
+int gd_workers_lookup_device(gd_handle* h, const gd_key* d_grains, uint32_t n, uint32_t* d_out_count,
+                             uint32_t* d_out_max_local, uint32_t* d_out_list);
+int gd_workers_lookup(gd_handle* h, const gd_key* grains, uint32_t n, uint32_t* out_count, uint32_t* out_max_local,
+                      uint32_t* out_list);
+int gd_workers_select_device(gd_handle* h, const gd_key* d_grains, uint32_t n, const int32_t* d_max_local,
+                             const uint32_t* d_draw, uint32_t ctx_base, uint32_t n_ctx, const uint8_t* d_ctx_flags,
+                             const uint32_t* d_num_running, const uint32_t* d_wait_offsets, uint32_t* d_ctx,
+                             uint8_t* d_pick, uint32_t* d_new_idx, uint32_t* d_n_new);
+/* Host pointers (the context arrays too; n_new a host word), synchronous. */
+int gd_workers_select(gd_handle* h, const gd_key* grains, uint32_t n, const int32_t* max_local, const uint32_t* draw,
+                      uint32_t ctx_base, uint32_t n_ctx, const uint8_t* ctx_flags, const uint32_t* num_running,
+                      const uint32_t* wait_offsets, uint32_t* out_ctx, uint8_t* out_pick, uint32_t* out_new_idx,
+                      uint32_t* n_new);
 
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */

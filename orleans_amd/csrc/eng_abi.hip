@@ -120,6 +120,8 @@ void gd_destroy(gd_handle* h) {
         for (DevBuf* b : {&h->gw_slots[t], &h->gw_side[t], &h->gw_ctr[t], &h->gw_last[t]}) free_buf(*b);
     free_buf(h->gw_state);
     for (DevBuf& b : h->gw_scr) free_buf(b);
+    for (DevBuf* b : {&h->wk_slots, &h->wk_side, &h->wk_ctr, &h->wk_last, &h->wk_state}) free_buf(*b);
+    for (DevBuf& b : h->wk_scr) free_buf(b);
     for (DevBuf& b : h->enc_tab) free_buf(b);
     for (DevBuf& b : h->enc_scr) free_buf(b);
     for (DevBuf& b : h->col_scr) free_buf(b);

@@ -194,6 +194,16 @@ struct gd_handle {
     int64_t gw_drop_timeout = 0, gw_route_expiry = 0;
     DevBuf gw_scr[6];                 // slot_of, is_new, scan flags, bucket counts, statuses / bucket ids unasked for
 
+    // stateless workers (gd_workers.h, eng_workers.hip): GrainId -> worker set; the 32-B slots, beside each
+    // {count, max_local, slot_capacity ctx words}, DevCounters + stripes, two election words a slot
+    DevBuf wk_slots, wk_side, wk_ctr, wk_last;
+    unsigned long long wk_cap = 0;
+    uint64_t wk_used_ub = 0;          // live + tombstones at most: the last read-back plus every possible add since
+    uint32_t wk_sc = 0;               // slot_capacity; 0: not configured (gd_workers_configure)
+    uint32_t wk_default_ml = 0;       // MaxLocal of a message that brings none
+    DevBuf wk_state;                  // the gated passes' deferred counts, then the find pass's miss count
+    DevBuf wk_scr[7];                 // slot_of, is_new, perm, offsets, rank, idle counts, scan flags
+
     // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
     // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads

@@ -34,6 +34,9 @@ PLACED_NONE, PLACED_NEW, PLACED_JOINED, PLACED_SKIPPED = range(4)
 MSG_READ_ONLY, MSG_ALWAYS_INTERLEAVE, MSG_MAY_INTERLEAVE = 1, 2, 4
 CTX_VALID, CTX_NOT_READY, CTX_INVALID, CTX_STATE_MASK = 0, 1, 2, 3
 CTX_HAS_RUNNING, CTX_RUNNING_READ_ONLY, CTX_REENTRANT, CTX_STATELESS_WORKER, CTX_STUCK = 4, 8, 16, 32, 64
+WK_NONE, WK_IDLE, WK_NEW, WK_RANDOM, WK_HELD = range(5)
+WK_NOT_GRAIN, WK_ADDED, WK_FULL = range(3)
+WK_MAX_SLOT_CAPACITY = 1024
 CB_NONE, CB_FIRE, CB_RESEND, CB_NO_CALLBACK, CB_GATEWAY_BACK, CB_TIMEOUT, CB_SILO_FAILED = range(7)
 CB_INVALIDATE_CACHE = 1
 RESP_TARGET_NOT_ME, RESP_HAS_CACHE_HEADER = 1, 2
@@ -94,6 +97,9 @@ EXPORTED_SYMBOLS = [
     "gd_gateway_routes_expire_device", "gd_gateway_routes_expire", "gd_gateway_lookup_device", "gd_gateway_lookup",
     "gd_gateway_deliver_device", "gd_gateway_deliver", "gd_gateway_send_queues_device", "gd_gateway_send_queues",
     "gd_gateway_ingress_device", "gd_gateway_ingress",
+    "gd_workers_configure", "gd_workers_clear", "gd_workers_count", "gd_workers_add_device", "gd_workers_add",
+    "gd_workers_remove_device", "gd_workers_remove", "gd_workers_lookup_device", "gd_workers_lookup",
+    "gd_workers_select_device", "gd_workers_select",
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
@@ -402,6 +408,17 @@ def _load() -> C.CDLL:
         "gd_gateway_send_queues": (C.c_int, [P] + [P] * 7 + [U32, C.c_int64] + [P] * 5),
         "gd_gateway_ingress_device": (C.c_int, [P, P, P, P, P, U32, C.c_int, P, P, P, P, P]),
         "gd_gateway_ingress": (C.c_int, [P, P, P, P, P, U32, C.c_int, P, P, P, P, P]),
+        "gd_workers_configure": (C.c_int, [P, U64, U32, U32]),
+        "gd_workers_clear": (C.c_int, [P]),
+        "gd_workers_count": (C.c_int, [P] + [C.POINTER(U64)] * 2),
+        "gd_workers_add_device": (C.c_int, [P, P, P, P, U32, P]),
+        "gd_workers_add": (C.c_int, [P, P, P, P, U32, P]),
+        "gd_workers_remove_device": (C.c_int, [P, P, P, U32, P]),
+        "gd_workers_remove": (C.c_int, [P, P, P, U32, P]),
+        "gd_workers_lookup_device": (C.c_int, [P, P, U32, P, P, P]),
+        "gd_workers_lookup": (C.c_int, [P, P, U32, P, P, P]),
+        "gd_workers_select_device": (C.c_int, [P, P, U32, P, P, U32, U32] + [P] * 7),
+        "gd_workers_select": (C.c_int, [P, P, U32, P, P, U32, U32] + [P] * 7),
         "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
         "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
@@ -1500,6 +1517,83 @@ class GrainDispatch:
         self._c(lib.gd_gateway_ingress_device(self.h, V(d_target_grain), V(d_sending_grain), V(d_direction), V(d_ttl), n,
                                               int(overloaded), V(d_out_status), V(d_out_silo), V(d_route_idx),
                                               V(d_n_route), V(d_route_keys)))
+
+    # -- stateless workers (Placement/StatelessWorkerDirector.cs, Catalog/ActivationDirectory.cs) ----------
+    def workers_configure(self, capacity: int, slot_capacity: int, default_max_local: int):
+        """gd_workers_configure: sets expected, list entries a set, MaxLocal of a message that brings none."""
+        self._c(lib.gd_workers_configure(self.h, capacity, slot_capacity, default_max_local))
+        self.workers_slot_capacity = slot_capacity
+
+    def workers_clear(self):
+        self._c(lib.gd_workers_clear(self.h))
+
+    def workers_count(self) -> Tuple[int, int]:
+        """gd_workers_count: (live sets, table slots)."""
+        v = [C.c_uint64(0) for _ in range(2)]
+        self._c(lib.gd_workers_count(self.h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
+    def workers_add(self, grains, ctx, max_local=None) -> np.ndarray:
+        """gd_workers_add: status u8[n] (WK_ADDED / WK_FULL / WK_NOT_GRAIN)."""
+        k, c = keys_array(grains), np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        ml = self._opt(max_local, np.int32)
+        st = np.zeros(len(k), np.uint8)
+        self._c(lib.gd_workers_add(self.h, _ptr(k), _ptr(c), None if ml is None else _ptr(ml), len(k), _ptr(st)))
+        return st
+
+    def workers_remove(self, grains, ctx) -> np.ndarray:
+        """gd_workers_remove: removed u8[n]."""
+        k, c = keys_array(grains), np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        out = np.zeros(len(k), np.uint8)
+        self._c(lib.gd_workers_remove(self.h, _ptr(k), _ptr(c), len(k), _ptr(out)))
+        return out
+
+    def workers_lookup(self, grains):
+        """gd_workers_lookup: (count u32[n], max_local u32[n], list u32[n, slot_capacity], unused tail 0xFFFFFFFF)."""
+        k = keys_array(grains)
+        n = len(k)
+        cnt, ml = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        lst = np.zeros((n, self.workers_slot_capacity), np.uint32)
+        self._c(lib.gd_workers_lookup(self.h, _ptr(k), n, _ptr(cnt), _ptr(ml), _ptr(lst)))
+        return cnt, ml, lst
+
+    def workers_select(self, grains, ctx_base: int, ctx_flags, num_running, wait_offsets=None, max_local=None,
+                       draw=None, new_list: bool = True):
+        """gd_workers_select: (ctx u32[n], pick u8[n], new_idx u32[n_new]) -- without new_list (ctx, pick)."""
+        k = keys_array(grains)
+        n = len(k)
+        cf, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        wo, ml, dr = self._opt(wait_offsets, np.uint32), self._opt(max_local, np.int32), self._opt(draw, np.uint32)
+        n_ctx = 0 if cf is None else len(cf)
+        p = lambda a: None if a is None or a.size == 0 else _ptr(a)
+        ctx, pick = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        ni = np.zeros(max(n, 1), np.uint32) if new_list else None
+        nn = np.zeros(1, np.uint32) if new_list else None
+        self._c(lib.gd_workers_select(self.h, _ptr(k), n, p(ml), p(dr), ctx_base, n_ctx, p(cf), p(nr), p(wo), _ptr(ctx),
+                                      _ptr(pick), p(ni), p(nn)))
+        return (ctx, pick, ni[:int(nn[0])].copy()) if new_list else (ctx, pick)
+
+    def workers_add_device(self, d_grains: int, d_ctx: int, d_max_local: Optional[int], n: int, d_out_status: int):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_workers_add_device(self.h, V(d_grains), V(d_ctx), V(d_max_local), n, V(d_out_status)))
+
+    def workers_remove_device(self, d_grains: int, d_ctx: int, n: int, d_out_removed: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_workers_remove_device(self.h, V(d_grains), V(d_ctx), n, V(d_out_removed)))
+
+    def workers_lookup_device(self, d_grains: int, n: int, d_out_count: Optional[int] = None,
+                              d_out_max_local: Optional[int] = None, d_out_list: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_workers_lookup_device(self.h, V(d_grains), n, V(d_out_count), V(d_out_max_local), V(d_out_list)))
+
+    def workers_select_device(self, d_grains: int, n: int, d_max_local: Optional[int], d_draw: Optional[int],
+                              ctx_base: int, n_ctx: int, d_ctx_flags: Optional[int], d_num_running: Optional[int],
+                              d_wait_offsets: Optional[int], d_ctx: int, d_pick: int, d_new_idx: Optional[int] = None,
+                              d_n_new: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_workers_select_device(self.h, V(d_grains), n, V(d_max_local), V(d_draw), ctx_base, n_ctx,
+                                             V(d_ctx_flags), V(d_num_running), V(d_wait_offsets), V(d_ctx), V(d_pick),
+                                             V(d_new_idx), V(d_n_new)))
 
     def upsert(self, keys, acts, silos) -> np.ndarray:
         """gd_dir_upsert: overwrite, the last item of a grain wins; acts may hold GD_ACT_MULTI."""
