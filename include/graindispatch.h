@@ -1854,6 +1854,55 @@ int gd_workers_select(gd_handle* h, const gd_key* grains, uint32_t n, const int3
                       const uint32_t* wait_offsets, uint32_t* out_ctx, uint8_t* out_pick, uint32_t* out_new_idx,
                       uint32_t* n_new);
 
+/* ---- compact route: (class, N1) records in, packed routes out ---------------------------
+ * A long-keyed grain's GrainId is {N0 = 0, N1 = the long key, TypeCodeData = one of the handle's few grain
+ * classes} (GrainId.GetGrainId(typeCode, long), GrainId.cs:72-77): 16 of its 24 bytes are constant.  These calls
+ * take such messages as records -- a class id (u8, the index into the handle's class table) and N1 (u32 or
+ * u64, zero-extended) -- and give the routes packed: act u32, silo u16, status u8.  A message costs 4, 5, 8 or 9
+ * bytes going up and 7 coming down (plus 4 of perm) instead of 24 and 9.
+ *
+ * gd_classes_set(type_code_data[n], n <= 256) replaces the handle's class table (n = 0 clears it); the class id
+ * is the array index.  It synchronises the handle's stream.  gd_classes_get gives up to max entries back and
+ * the table's size in *out_n.
+ *
+ * Input, structure-of-arrays: cls[n] (NULL: every message is class 0) and n1[n] of n1_width 4 (uint32_t) or 8
+ * (uint64_t) bytes.  Output: out_act[n], out_silo16[n], out_status[n]; the bucket forms also perm[n] and
+ * offsets[n_act + 2], exactly as gd_route_bucket gives them (misses in the trailing bucket).
+ *
+ * For each message the key is {0, n1[i], classes[cls[i]]} and (act, silo, status) are what gd_route* gives
+ * for that key -- GD_ROUTE_OK, _MISS, _SYSTEM_TARGET, _MEMBERSHIP, _KEYEXT (a class of a KeyExt category; its
+ * string never reaches these calls) and _MULTI_ACT -- in every ring mode, and in LocalLookup (cache) mode with
+ * the same cache hits and LRU touches in the same batch order.  Two values are these calls' own:
+ *   GD_NO_SILO16        GD_NO_SILO as 16 bits.
+ *   GD_ROUTE_BAD_CLASS  cls[i] is not below the table's size: act = GD_NO_ACTIVATION, silo = GD_NO_SILO16; in
+ *                       LocalLookup mode the message touches no cache entry and counts no access.
+ * A silo index in 0xFFFF..0xFFFFFFFE does not fit: GD_NO_SILO16 is stored and the message counted.  The
+ * directory, the cache and the ring hold silo indexes up to 0xFFFE, so only cfg.my_silo (system targets) and
+ * cfg.seed_silo (the membership grain) can be that wide.  The host forms synchronise, bring every result down
+ * and then return GD_EINVAL when the count is not zero; the device forms store the count in *d_wide (optional,
+ * NULL allowed; zeroed by the call on the handle's stream).
+ *
+ * Errors: GD_EINVAL for an n1_width other than 4 or 8 and for null arguments; with n > 0, GD_ESTATE when no
+ * class table is set (class 0 is absent, whether cls is NULL or not).  n = 0 is GD_OK and the bucket forms
+ * write offsets.  Host forms: pinned buffers (gd_host_alloc) of at least two GD_OPT_HOST_CHUNK chunks take
+ * gd_route_bucket's copy / route / copy pipeline over the record streams, anything else one copy each way. */
+#define GD_NO_SILO16       0xFFFFu
+#define GD_ROUTE_BAD_CLASS 8
+int gd_classes_set(gd_handle* h, const uint64_t* type_code_data, uint32_t n);
+int gd_classes_get(gd_handle* h, uint64_t* out_type_code_data, uint32_t max, uint32_t* out_n);
+int gd_route_compact(gd_handle* h, const uint8_t* cls, const void* n1, uint32_t n1_width, uint32_t n, uint32_t* out_act,
+                     uint16_t* out_silo16, uint8_t* out_status);
+int gd_route_bucket_compact(gd_handle* h, const uint8_t* cls, const void* n1, uint32_t n1_width, uint32_t n,
+                            uint32_t n_act, uint32_t* out_act, uint16_t* out_silo16, uint8_t* out_status,
+                            uint32_t* out_perm, uint32_t* out_offsets);
+/* Device pointers, on the handle's stream, no synchronisation (the bucketing as gd_route_bucket_device's:
+ * on the bucket stream when one is set). */
+int gd_route_compact_device(gd_handle* h, const uint8_t* d_cls, const void* d_n1, uint32_t n1_width, uint32_t n,
+                            uint32_t* d_act, uint16_t* d_silo16, uint8_t* d_status, uint32_t* d_wide);
+int gd_route_bucket_compact_device(gd_handle* h, const uint8_t* d_cls, const void* d_n1, uint32_t n1_width, uint32_t n,
+                                   uint32_t n_act, uint32_t* d_act, uint16_t* d_silo16, uint8_t* d_status,
+                                   uint32_t* d_perm, uint32_t* d_offsets, uint32_t* d_wide);
+
 /* ---- per-kernel timing (cfg.flags & GD_CFG_KERNEL_TIMING) ----------------------- */
 /* Up to max entries of {name, launches, total_ms} accumulated since the last reset. */
 typedef struct gd_kernel_time {

@@ -122,6 +122,7 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->gw_scr) free_buf(b);
     for (DevBuf* b : {&h->wk_slots, &h->wk_side, &h->wk_ctr, &h->wk_last, &h->wk_state}) free_buf(*b);
     for (DevBuf& b : h->wk_scr) free_buf(b);
+    for (DevBuf* b : {&h->cls_tab, &h->cls_wide, &h->cls_silo}) free_buf(*b);
     for (DevBuf& b : h->enc_tab) free_buf(b);
     for (DevBuf& b : h->enc_scr) free_buf(b);
     for (DevBuf& b : h->col_scr) free_buf(b);
@@ -436,6 +437,31 @@ int claim_passes(gd_handle* h, bool actdir, const gd_key* dk, uint32_t n, uint32
 }
 }  // namespace gdx
 
+namespace gdx {
+
+// The bucketing that follows a device route (gd_route_bucket_device and its compact form): on the handle's
+// stream, or with gd_set_bucket_stream on the bucket stream once the route is done, so that the handle's
+// stream goes on to the next batch's route.
+int bucket_after_route(gd_handle* h, const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32_t* d_perm,
+                       uint32_t* d_offsets) {
+    if (!h->bstream || h->bstream == h->stream) return bucket_device(h, d_act, n, n_act, d_perm, d_offsets);
+    HIP_TRY(h, hipEventRecord(h->b_ev, h->stream));
+    HIP_TRY(h, hipStreamWaitEvent(h->bstream, h->b_ev, 0));
+    const hipStream_t main = h->stream;
+    const bool measured_before = h->measured_launch;
+    h->measured_launch = false;
+    h->stream = h->bstream;
+    const int r = bucket_device(h, d_act, n, n_act, d_perm, d_offsets);
+    h->stream = main;
+    h->b_pending = true;
+    // a bucketing timed for tune_choose runs alone: the next batch's route waits for it (ADVICE r05)
+    if (h->measured_launch) GD_TRY(bfence(h));
+    h->measured_launch = h->measured_launch || measured_before;
+    return r;
+}
+
+}  // namespace gdx
+
 extern "C" {
 
 int gd_dir_register(gd_handle* h, const gd_key* keys, const gd_val* vals, uint32_t n, gd_val* out_vals,
@@ -621,22 +647,7 @@ int gd_route_bucket_device(gd_handle* h, const gd_key* d_keys, uint32_t n, uint3
     if (!h || !d_offsets || (n && (!d_keys || !d_silo || !d_act || !d_status || !d_perm)))
         return set_err(h, GD_EINVAL, "null argument");
     if (n) GD_TRY(route_device(h, d_keys, n, d_silo, d_act, d_status));
-    if (!h->bstream || h->bstream == h->stream) return bucket_device(h, d_act, n, n_act, d_perm, d_offsets);
-    // the bucketing on the bucket stream once this route is done; the handle's stream goes on to the
-    // next batch's route (gd_set_bucket_stream)
-    HIP_TRY(h, hipEventRecord(h->b_ev, h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->bstream, h->b_ev, 0));
-    const hipStream_t main = h->stream;
-    const bool measured_before = h->measured_launch;
-    h->measured_launch = false;
-    h->stream = h->bstream;
-    const int r = bucket_device(h, d_act, n, n_act, d_perm, d_offsets);
-    h->stream = main;
-    h->b_pending = true;
-    // a bucketing timed for tune_choose runs alone: the next batch's route waits for it (ADVICE r05)
-    if (h->measured_launch) GD_TRY(bfence(h));
-    h->measured_launch = h->measured_launch || measured_before;
-    return r;
+    return bucket_after_route(h, d_act, n, n_act, d_perm, d_offsets);
 }
 
 int gd_set_bucket_stream(gd_handle* h, void* s) {

@@ -13,7 +13,7 @@ namespace gdx {
 // in that same call.  Built (a memset and k_cxd_build on the route's stream, right before the route --
 // the stream order the PURE form rests on) only when the previous k_route launch on this handle found the
 // index pure under the same snapshot id: a directory that changes between routes never pays for it.
-static int cxd_prepare(gd_handle* h, bool cx, int var, bool* use, CxdArgs* d) {
+int cxd_prepare(gd_handle* h, bool cx, int var, bool* use, CxdArgs* d) {
     *use = false;
     const bool pure = cx && h->cx8_pure;
     const uint64_t snap = h->cx_snap + h->tab_gen;
@@ -45,9 +45,6 @@ static int cxd_prepare(gd_handle* h, bool cx, int var, bool* use, CxdArgs* d) {
     return GD_OK;
 }
 #endif
-
-// The probe index up to which the routes read their key stream non-temporally (route_mode).
-constexpr uint64_t ROUTE_NT_INDEX_BYTES = 64ull << 20;
 
 // Every k_route launch of one (ring mode, messages a thread M, key width N1W) over the form the tuner
 // picks (cx_choose kind 0 / 1).  N1W = 0: 24-B keys, with tcd = 0, rcnt = nullptr, world = 0, src =
@@ -226,23 +223,11 @@ bool host_pinned(const void* p) {
     return a.type == hipMemoryTypeHost;
 }
 
-// Host buffers, large batch: the PCIe copies overlap the kernels.  Chunk k's keys go up on the
-// copy-in stream while chunk k-1 is probed on the handle's stream and chunk k-2's routes come
-// down on the copy-out stream (PCIe is full duplex); the bucketing needs the whole batch, so only
-// perm and offsets are copied after it.  Bounded by the 24-B-a-message upload instead of the sum
-// of both directions.  Used when the caller's buffers are pinned (gd_host_alloc).  out_perm ==
-// nullptr: gd_route (routes only, no bucketing).
+// gd_route / gd_route_bucket on pinned host buffers, large batch: host_pipeline (gd_engine.h) over the 24-B
+// key stream up and silo / act / status down; bounded by the 24-B-a-message upload instead of the sum of
+// both directions.  out_perm == nullptr: gd_route (routes only, no bucketing).
 int route_bucket_host_pipelined(gd_handle* h, const gd_key* keys, uint32_t n, uint32_t n_act, uint32_t* out_silo,
                                 uint32_t* out_act, uint8_t* out_status, uint32_t* out_perm, uint32_t* out_offsets) {
-    if (!h->cin) HIP_TRY(h, hipStreamCreateWithFlags(&h->cin, hipStreamNonBlocking));
-    if (!h->cout) HIP_TRY(h, hipStreamCreateWithFlags(&h->cout, hipStreamNonBlocking));
-    const uint32_t C = h->host_chunk;
-    const uint32_t nch = (uint32_t)(((uint64_t)n + C - 1) / C);
-    while (h->hp_ev.size() < 2 * (size_t)nch + 2) {
-        hipEvent_t e;
-        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        h->hp_ev.push_back(e);
-    }
     GD_TRY(ensure(h, h->keys_in, (size_t)n * sizeof(gd_key)));
     GD_TRY(ensure(h, h->out_a, (size_t)n * 4 + 4));
     GD_TRY(ensure(h, h->out_b, (size_t)n * 4 + 4));
@@ -256,33 +241,13 @@ int route_bucket_host_pipelined(gd_handle* h, const gd_key* keys, uint32_t n, ui
     uint32_t* silo = (uint32_t*)h->out_a.p;
     uint32_t* act = (uint32_t*)h->out_b.p;
     uint8_t* st = (uint8_t*)h->out_c.p;
-    hipEvent_t* ev = h->hp_ev.data();
-    HIP_TRY(h, hipEventRecord(ev[2 * nch], h->stream));        // earlier work on the handle's stream
-    HIP_TRY(h, hipStreamWaitEvent(h->cin, ev[2 * nch], 0));
-    for (uint32_t k = 0; k < nch; ++k) {
-        const size_t off = (size_t)k * C;
-        const uint32_t cnt = (uint32_t)std::min<size_t>(C, n - off);
-        HIP_TRY(h, hipMemcpyAsync(dk + off, keys + off, (size_t)cnt * sizeof(gd_key), hipMemcpyHostToDevice, h->cin));
-        HIP_TRY(h, hipEventRecord(ev[2 * k], h->cin));
-        HIP_TRY(h, hipStreamWaitEvent(h->stream, ev[2 * k], 0));
-        GD_TRY(route_device(h, dk + off, cnt, silo + off, act + off, st + off));
-        HIP_TRY(h, hipEventRecord(ev[2 * k + 1], h->stream));
-        HIP_TRY(h, hipStreamWaitEvent(h->cout, ev[2 * k + 1], 0));
-        HIP_TRY(h, hipMemcpyAsync(out_silo + off, silo + off, (size_t)cnt * 4, hipMemcpyDeviceToHost, h->cout));
-        HIP_TRY(h, hipMemcpyAsync(out_act + off, act + off, (size_t)cnt * 4, hipMemcpyDeviceToHost, h->cout));
-        HIP_TRY(h, hipMemcpyAsync(out_status + off, st + off, cnt, hipMemcpyDeviceToHost, h->cout));
-    }
-    if (!bucket) {
-        HIP_TRY(h, hipStreamSynchronize(h->cout));
-        return sync(h);
-    }
-    GD_TRY(bucket_device(h, act, n, n_act, (uint32_t*)h->u8_a.p, (uint32_t*)h->offs.p));
-    HIP_TRY(h, hipEventRecord(ev[2 * nch + 1], h->stream));
-    HIP_TRY(h, hipStreamWaitEvent(h->cout, ev[2 * nch + 1], 0));
-    HIP_TRY(h, hipMemcpyAsync(out_perm, h->u8_a.p, (size_t)n * 4, hipMemcpyDeviceToHost, h->cout));
-    HIP_TRY(h, hipMemcpyAsync(out_offsets, h->offs.p, ((size_t)n_act + 2) * 4, hipMemcpyDeviceToHost, h->cout));
-    HIP_TRY(h, hipStreamSynchronize(h->cout));
-    return sync_checked(h);
+    const HpStream up[1] = {{(void*)keys, dk, sizeof(gd_key)}};
+    const HpStream down[3] = {{out_silo, silo, 4}, {out_act, act, 4}, {out_status, st, 1}};
+    const HpTail tail[2] = {{out_perm, h->u8_a.p, (size_t)n * 4}, {out_offsets, h->offs.p, ((size_t)n_act + 2) * 4}};
+    return host_pipeline(
+        h, n, up, 1, down, 3,
+        [&](size_t off, uint32_t cnt) { return route_device(h, dk + off, cnt, silo + off, act + off, st + off); }, act,
+        n_act, bucket ? (uint32_t*)h->u8_a.p : nullptr, bucket ? (uint32_t*)h->offs.p : nullptr, tail, bucket ? 2 : 0);
 }
 
 }  // namespace gdx

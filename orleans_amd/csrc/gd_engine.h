@@ -204,6 +204,12 @@ struct gd_handle {
     DevBuf wk_state;                  // the gated passes' deferred counts, then the find pass's miss count
     DevBuf wk_scr[7];                 // slot_of, is_new, perm, offsets, rank, idle counts, scan flags
 
+    // compact route (gd_compact.h, eng_compact.hip): the class table (class id -> TypeCodeData; gd_classes_set) on
+    // the device and on the host, the count of silos too wide for 16 bits, and the simple form's 32-bit silos
+    DevBuf cls_tab;
+    std::vector<uint64_t> cls_host;   // empty: no table set
+    DevBuf cls_wide, cls_silo;
+
     // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
     // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads
@@ -470,6 +476,15 @@ int grow_table(gd_handle* h, uint64_t incoming);
 int fwd_pack(gd_handle* h, const gd_key* keys, const uint8_t* st, const uint32_t* silo, uint32_t n, uint32_t n_shards,
              uint32_t my_rank, void* out_keys, uint32_t* out_pos, uint32_t* counts, const uint32_t* n1 = nullptr);
 bool host_pinned(const void* p);
+// The probe index up to which the routes read their key stream non-temporally (route_mode).
+constexpr uint64_t ROUTE_NT_INDEX_BYTES = 64ull << 20;
+#if GD_DIRECT_INDEX
+int cxd_prepare(gd_handle* h, bool cx, int var, bool* use, CxdArgs* d);
+#endif
+int compact_route_device(gd_handle* h, const uint8_t* cls, const void* n1s, uint32_t n1w, uint32_t n, uint32_t* act,
+                         uint16_t* silo16, uint8_t* status, uint32_t* wide);
+int bucket_after_route(gd_handle* h, const uint32_t* d_act, uint32_t n, uint32_t n_act, uint32_t* d_perm,
+                       uint32_t* d_offsets);
 int route_bucket_host_pipelined(gd_handle* h, const gd_key* keys, uint32_t n, uint32_t n_act, uint32_t* out_silo,
                                 uint32_t* out_act, uint8_t* out_status, uint32_t* out_perm, uint32_t* out_offsets);
 int register_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, uint32_t n, gd_val* out_vals,
@@ -723,6 +738,70 @@ struct HostStage {
         return GD_OK;
     }
 };
+
+// ---- the pipelined host route (gd_route / gd_route_bucket and their compact forms on pinned buffers)
+// One per-message array of the call: elem bytes a message, its host and its device end.
+struct HpStream {
+    void* host;
+    void* dev;
+    size_t elem;
+};
+// An array brought down whole after the last chunk (and the bucketing).
+struct HpTail {
+    void* host;
+    const void* dev;
+    size_t bytes;
+};
+
+// Host buffers, large batch: the PCIe copies overlap the kernels.  Chunk k's inputs (up[]) go up on the
+// copy-in stream while chunk k-1 is routed on the handle's stream -- route(off, cnt) enqueues it -- and
+// chunk k-2's routes (down[]) come down on the copy-out stream (PCIe is full duplex); the bucketing
+// (d_perm != nullptr: of d_act into d_perm / d_offs) needs the whole batch, so it and the tail[] copies
+// follow the last chunk.  Bounded by the slower direction's bytes instead of the sum of both.  Used when
+// the caller's buffers are pinned (gd_host_alloc).
+template <typename Route>
+int host_pipeline(gd_handle* h, uint32_t n, const HpStream* up, int n_up, const HpStream* down, int n_down, Route route,
+                  const uint32_t* d_act, uint32_t n_act, uint32_t* d_perm, uint32_t* d_offs, const HpTail* tail,
+                  int n_tail) {
+    if (!h->cin) HIP_TRY(h, hipStreamCreateWithFlags(&h->cin, hipStreamNonBlocking));
+    if (!h->cout) HIP_TRY(h, hipStreamCreateWithFlags(&h->cout, hipStreamNonBlocking));
+    const uint32_t C = h->host_chunk;
+    const uint32_t nch = (uint32_t)(((uint64_t)n + C - 1) / C);
+    while (h->hp_ev.size() < 2 * (size_t)nch + 2) {
+        hipEvent_t e;
+        HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        h->hp_ev.push_back(e);
+    }
+    hipEvent_t* ev = h->hp_ev.data();
+    HIP_TRY(h, hipEventRecord(ev[2 * nch], h->stream));        // earlier work on the handle's stream
+    HIP_TRY(h, hipStreamWaitEvent(h->cin, ev[2 * nch], 0));
+    for (uint32_t k = 0; k < nch; ++k) {
+        const size_t off = (size_t)k * C;
+        const uint32_t cnt = (uint32_t)std::min<size_t>(C, n - off);
+        for (int s = 0; s < n_up; ++s)
+            HIP_TRY(h, hipMemcpyAsync((char*)up[s].dev + off * up[s].elem, (const char*)up[s].host + off * up[s].elem,
+                                      (size_t)cnt * up[s].elem, hipMemcpyHostToDevice, h->cin));
+        HIP_TRY(h, hipEventRecord(ev[2 * k], h->cin));
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, ev[2 * k], 0));
+        GD_TRY(route(off, cnt));
+        HIP_TRY(h, hipEventRecord(ev[2 * k + 1], h->stream));
+        HIP_TRY(h, hipStreamWaitEvent(h->cout, ev[2 * k + 1], 0));
+        for (int s = 0; s < n_down; ++s)
+            HIP_TRY(h, hipMemcpyAsync((char*)down[s].host + off * down[s].elem,
+                                      (const char*)down[s].dev + off * down[s].elem, (size_t)cnt * down[s].elem,
+                                      hipMemcpyDeviceToHost, h->cout));
+    }
+    const bool bucket = d_perm != nullptr;          // else routes only, no bucketing
+    if (bucket) GD_TRY(bucket_device(h, d_act, n, n_act, d_perm, d_offs));
+    if (bucket || n_tail) {
+        HIP_TRY(h, hipEventRecord(ev[2 * nch + 1], h->stream));
+        HIP_TRY(h, hipStreamWaitEvent(h->cout, ev[2 * nch + 1], 0));
+        for (int s = 0; s < n_tail; ++s)
+            HIP_TRY(h, hipMemcpyAsync(tail[s].host, tail[s].dev, tail[s].bytes, hipMemcpyDeviceToHost, h->cout));
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->cout));
+    return bucket ? sync_checked(h) : sync(h);
+}
 
 // ---- the stages that keep a table of their own (the callback table, the gateway's two)
 // The claim passes of a batch (gd_dirbatch.h) over the `passes` words of `retry`, zeroed here: run(p, gate,

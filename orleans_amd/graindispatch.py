@@ -24,6 +24,8 @@ ROUTE_ADDRESSED, ROUTE_UNDECODED = 5, 6
 FRAME_HAS_TARGET, FRAME_COMPLETE, FRAME_FALLBACK, FRAME_MALFORMED, FRAME_TARGET_KEYEXT = 1, 2, 4, 8, 16
 NO_ACTIVATION = 0xFFFFFFFF
 NO_SILO = 0xFFFFFFFF
+NO_SILO16 = 0xFFFF            # GD_NO_SILO16: the compact routes' packed GD_NO_SILO
+GD_ROUTE_BAD_CLASS = 8        # gd_route_compact*: the class id is not in the class table
 TTL_NONE = (1 << 63) - 1
 (SEND_QUEUED, SEND_LOOPBACK, SEND_EXPIRED, SEND_NO_SILO, SEND_UNKNOWN_SILO, SEND_THROWS,
  SEND_HELD) = range(7)
@@ -100,6 +102,8 @@ EXPORTED_SYMBOLS = [
     "gd_workers_configure", "gd_workers_clear", "gd_workers_count", "gd_workers_add_device", "gd_workers_add",
     "gd_workers_remove_device", "gd_workers_remove", "gd_workers_lookup_device", "gd_workers_lookup",
     "gd_workers_select_device", "gd_workers_select",
+    "gd_classes_set", "gd_classes_get", "gd_route_compact", "gd_route_bucket_compact", "gd_route_compact_device",
+    "gd_route_bucket_compact_device",
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
@@ -419,6 +423,12 @@ def _load() -> C.CDLL:
         "gd_workers_lookup": (C.c_int, [P, P, U32, P, P, P]),
         "gd_workers_select_device": (C.c_int, [P, P, U32, P, P, U32, U32] + [P] * 7),
         "gd_workers_select": (C.c_int, [P, P, U32, P, P, U32, U32] + [P] * 7),
+        "gd_classes_set": (C.c_int, [P, P, U32]),
+        "gd_classes_get": (C.c_int, [P, P, U32, C.POINTER(U32)]),
+        "gd_route_compact": (C.c_int, [P, P, P, U32, U32, P, P, P]),
+        "gd_route_bucket_compact": (C.c_int, [P, P, P, U32, U32, U32, P, P, P, P, P]),
+        "gd_route_compact_device": (C.c_int, [P, P, P, U32, U32, P, P, P, P]),
+        "gd_route_bucket_compact_device": (C.c_int, [P, P, P, U32, U32, U32, P, P, P, P, P, P]),
         "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
         "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
@@ -1688,6 +1698,69 @@ class GrainDispatch:
         off = np.zeros(n_act + 2, dtype=np.uint32)
         self._c(lib.gd_route_bucket(self.h, _ptr(k), n, n_act, _ptr(silo), _ptr(act), _ptr(st), _ptr(perm), _ptr(off)))
         return st, silo, act, perm, off
+
+    # -- compact route: (class, N1) records in, packed routes out -----------
+    def classes_set(self, type_code_data):
+        """gd_classes_set: the class table; class id = index.  An empty list clears it."""
+        t = np.ascontiguousarray(np.asarray(type_code_data, dtype=np.uint64))
+        self._c(lib.gd_classes_set(self.h, _ptr(t) if len(t) else None, len(t)))
+
+    def classes_get(self) -> np.ndarray:
+        out = np.zeros(256, dtype=np.uint64)
+        n = C.c_uint32(0)
+        self._c(lib.gd_classes_get(self.h, _ptr(out), 256, C.byref(n)))
+        return out[: n.value].copy()
+
+    @staticmethod
+    def _records(cls, n1, n1_width):
+        """(cls u8[n] or None, n1 u32[n] / u64[n], width): n1_width None takes the width of n1's dtype (4 for a
+        4-byte integer array, else 8)."""
+        a = np.asarray(n1)
+        w = n1_width or (4 if a.dtype.kind in "iu" and a.dtype.itemsize == 4 else 8)
+        a = np.ascontiguousarray(a, dtype=np.uint32 if w == 4 else np.uint64)
+        c = None if cls is None else np.ascontiguousarray(np.asarray(cls, dtype=np.uint8))
+        assert c is None or len(c) == len(a), "one class id per N1"
+        return c, a, w
+
+    def route_compact(self, cls, n1, n1_width: Optional[int] = None):
+        """gd_route_compact: (status u8[n], silo16 u16[n], act u32[n]) of the keys {0, n1[i], classes[cls[i]]};
+        cls None: every message is class 0."""
+        c, a, w = self._records(cls, n1, n1_width)
+        n = len(a)
+        act = np.zeros(n, dtype=np.uint32)
+        silo = np.zeros(n, dtype=np.uint16)
+        st = np.zeros(n, dtype=np.uint8)
+        self._c(lib.gd_route_compact(self.h, None if c is None else _ptr(c), _ptr(a), w, n, _ptr(act), _ptr(silo),
+                                     _ptr(st)))
+        return st, silo, act
+
+    def route_bucket_compact(self, cls, n1, n_act: int, n1_width: Optional[int] = None):
+        """gd_route_bucket_compact: (status, silo16, act, perm u32[n], offsets u32[n_act + 2])."""
+        c, a, w = self._records(cls, n1, n1_width)
+        n = len(a)
+        act = np.zeros(n, dtype=np.uint32)
+        silo = np.zeros(n, dtype=np.uint16)
+        st = np.zeros(n, dtype=np.uint8)
+        perm = np.zeros(n, dtype=np.uint32)
+        off = np.zeros(n_act + 2, dtype=np.uint32)
+        self._c(lib.gd_route_bucket_compact(self.h, None if c is None else _ptr(c), _ptr(a), w, n, n_act, _ptr(act),
+                                            _ptr(silo), _ptr(st), _ptr(perm), _ptr(off)))
+        return st, silo, act, perm, off
+
+    def route_compact_device(self, d_cls: Optional[int], d_n1: int, n1_width: int, n: int, d_act: int, d_silo16: int,
+                             d_status: int, d_wide: Optional[int] = None):
+        """gd_route_compact_device: device pointers, enqueue only; d_wide (optional) gets the count of silos that
+        do not fit 16 bits."""
+        V = C.c_void_p
+        self._c(lib.gd_route_compact_device(self.h, V(d_cls), V(d_n1), n1_width, n, V(d_act), V(d_silo16), V(d_status),
+                                            V(d_wide)))
+
+    def route_bucket_compact_device(self, d_cls: Optional[int], d_n1: int, n1_width: int, n: int, n_act: int,
+                                    d_act: int, d_silo16: int, d_status: int, d_perm: int, d_offsets: int,
+                                    d_wide: Optional[int] = None):
+        V = C.c_void_p
+        self._c(lib.gd_route_bucket_compact_device(self.h, V(d_cls), V(d_n1), n1_width, n, n_act, V(d_act), V(d_silo16),
+                                                   V(d_status), V(d_perm), V(d_offsets), V(d_wide)))
 
     # -- KeyExt grains (string keys, compound keys, geo clients) ------------------------
     @staticmethod

@@ -980,6 +980,65 @@ private:
     LocalGrainDirectory& dir_;
 };
 
+// The compact route (gd_route_compact*) for long-keyed grains: a GrainId from
+// GrainId.GetGrainId(typeCode, long) (GrainId.cs:72-77) is {N0 = 0, N1 = the long key, TypeCodeData of its class}, so
+// a message is sent as (class id, N1) and comes back as act u32 / silo u16 / status u8.  SetClasses installs the
+// class table (the class id is the index); ClassOf gives a key's record, or false when the key is not long-keyed or
+// its class is not in the table (route it with the 24-B calls).
+struct CompactRoutes {
+    std::vector<uint32_t> Act;        // GD_NO_ACTIVATION unless Status is GD_ROUTE_OK
+    std::vector<uint16_t> Silo;       // index into the SiloTable; GD_NO_SILO16 = none
+    std::vector<uint8_t> Status;      // GD_ROUTE_*, GD_ROUTE_BAD_CLASS
+    std::vector<uint32_t> Perm, Offsets;   // RouteBucket only: gd_route_bucket's stable bucketing by activation
+};
+
+class CompactRouter {
+public:
+    explicit CompactRouter(gd_handle* h) : h_(h) {}
+    void SetClasses(const std::vector<uint64_t>& typeCodeData) {
+        Check(h_, gd_classes_set(h_, typeCodeData.data(), (uint32_t)typeCodeData.size()));
+        classes_ = typeCodeData;
+    }
+    const std::vector<uint64_t>& Classes() const { return classes_; }
+    bool ClassOf(const UniqueKey& k, uint8_t& cls, uint64_t& n1) const {
+        const gd_key g = k.ToNative();
+        if (g.n0 != 0) return false;
+        for (size_t c = 0; c < classes_.size(); ++c)
+            if (classes_[c] == g.type_code_data) {
+                cls = (uint8_t)c;
+                n1 = g.n1;
+                return true;
+            }
+        return false;
+    }
+    // cls empty: every message is class 0.
+    CompactRoutes Route(const std::vector<uint8_t>& cls, const std::vector<uint64_t>& n1) {
+        CompactRoutes r = Sized(n1.size());
+        Check(h_, gd_route_compact(h_, cls.empty() ? nullptr : cls.data(), n1.data(), 8, (uint32_t)n1.size(), r.Act.data(),
+                                   r.Silo.data(), r.Status.data()));
+        return r;
+    }
+    CompactRoutes RouteBucket(const std::vector<uint8_t>& cls, const std::vector<uint64_t>& n1, uint32_t nAct) {
+        CompactRoutes r = Sized(n1.size());
+        r.Perm.resize(n1.size());
+        r.Offsets.resize((size_t)nAct + 2);
+        Check(h_, gd_route_bucket_compact(h_, cls.empty() ? nullptr : cls.data(), n1.data(), 8, (uint32_t)n1.size(), nAct,
+                                          r.Act.data(), r.Silo.data(), r.Status.data(), r.Perm.data(), r.Offsets.data()));
+        return r;
+    }
+
+private:
+    static CompactRoutes Sized(size_t n) {
+        CompactRoutes r;
+        r.Act.resize(n);
+        r.Silo.resize(n);
+        r.Status.resize(n);
+        return r;
+    }
+    gd_handle* h_;
+    std::vector<uint64_t> classes_;
+};
+
 // ActivationDirectory (src/Orleans.Runtime/Catalog/ActivationDirectory.cs): ActivationId -> the
 // scheduling context (index) of an activation or system target, with its state, in the GPU table.
 class ActivationDirectory {
