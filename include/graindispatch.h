@@ -1204,8 +1204,9 @@ int gd_route_place_bucket(gd_handle* h, const gd_key* keys, uint32_t n, const ui
  *
  * Left to C#: deadlock detection (:277-293, off by default), the interface-version check of
  * HandleIncomingRequest (:403-410), logging (TryRescheduleCollection, :118: gd_collect_touch*), and the cross-cluster return in
- * TryForwardRequest.  A frame-fed form is not offered: gd_frame_fields has no read-only / interleave / TTL /
- * forward-count outputs, and growing that struct breaks its callers (GD_ABI_VERSION stays 1). */
+ * TryForwardRequest.  The frame-fed form is gd_receive_turns_frames* (below): the decoder gives the read-only /
+ * interleave / TTL / forward-count headers through gd_frame_turn_fields, a second struct beside gd_frame_fields
+ * (which keeps its layout: GD_ABI_VERSION stays 1). */
 #define GD_TURN_NONE              0
 #define GD_TURN_START             1
 #define GD_TURN_WAIT              2
@@ -1261,6 +1262,67 @@ int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd
                             const gd_key* d_sending_activation, const gd_turn_state* state, uint8_t* d_turn,
                             uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
                             uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets);
+
+/* ---- turn headers from the receive buffer ---------------------------------------------
+ * The headers the turn stage and the callback table read, out of the same walk as gd_decode_frames
+ * (HeadersContainer.Deserializer, Message.cs:1247-1356): one pass over the frames, one staging of each frame's
+ * window.  n entries each; any pointer may be NULL (the field is not stored).
+ *   - a bool is true iff its byte is SerializationTokenType.True (ReadBool, :1358-1361); any other byte, and a
+ *     header bit set with a False token, reads 0.  The IS_NEW_PLACEMENT / IS_UNORDERED bytes are skipped.
+ *   - a GD_FRAME_MALFORMED frame, and a GD_FRAME_FALLBACK one whose mask has CacheInvalidationHeader or
+ *     RequestContext, has the absent value in every field (as it has zero keys); a frame that is FALLBACK only
+ *     for its TargetObserver has all of them decoded (they precede it on the wire).
+ *   - a present TimeToLive of TimeSpan.MaxValue equals GD_TTL_NONE: both mean "never expires", so the turn
+ *     stage treats them alike.
+ *   - ForwardCount is clamped to [0, 255] (gd_turns' byte); the reference never writes a negative one, which
+ *     reads 0. */
+typedef struct gd_frame_turn_fields {
+    int64_t* ttl;             /* TimeToLive as written (TimeSpan ticks); GD_TTL_NONE when absent       */
+    uint8_t* forward_count;   /* ForwardCount clamped to [0, 255]; 0 when absent                        */
+    uint8_t* msg_flags;       /* GD_MSG_READ_ONLY | GD_MSG_ALWAYS_INTERLEAVE from the two bool tokens   */
+    uint8_t* result;          /* Message.ResponseTypes byte; 0 when absent                              */
+    uint8_t* rejection_type;  /* Message.RejectionTypes byte; 0 when absent                             */
+    int32_t* resend_count;    /* 0 when absent                                                          */
+} gd_frame_turn_fields;
+/* gd_decode_frames* with the turn headers.  d_turn_out NULL (or all of its pointers NULL): exactly
+ * gd_decode_frames*.  d_out->flags and d_out->target_grain stay required.  Device form: enqueue only. */
+int gd_decode_frames_turn_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                                 uint32_t n, const gd_frame_fields* d_out, const gd_frame_turn_fields* d_turn_out);
+/* Host pointers; synchronous. */
+int gd_decode_frames_turn(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                          const gd_frame_fields* out, const gd_frame_turn_fields* turn_out);
+/* Receive buffer -> decode -> IncomingMessageAgent.ReceiveMessage -> Dispatcher.ReceiveRequest with no host round
+ * trip: gd_receive_frames_device, then the turn stage on its outputs and on the decoded direction, ttl, forward
+ * count, flags, TargetActivation and SendingActivation (the call-chain test compares the decoded two).
+ *   buffer .. d_offsets      as gd_receive_frames_device; d_out may be NULL (a non-NULL one needs flags and
+ *                            target_grain), and names the decoded fields the caller wants back
+ *   d_turn_out               may be NULL; names the turn headers the caller wants back, as the wire has them
+ *                            (before ttl_age_ticks and d_msg_flags_or).  What is not asked for is decoded into
+ *                            scratch of the handle
+ *   ttl_age_ticks >= 0       Message.TimeToLive's getter is _timeToLive - (UtcNow - _localCreationTime)
+ *                            (Message.cs:992-1002): the turn stage reads wire ttl - ttl_age_ticks for a ttl
+ *                            with a value, saturating at INT64_MIN; GD_TTL_NONE stays.  < 0: GD_EINVAL
+ *   d_msg_flags_or           NULL, or one GD_MSG_* byte a message OR-ed into the decoded flags: where C# puts
+ *                            GD_MSG_MAY_INTERLEAVE (user code)
+ *   state .. d_wait_offsets  as gd_receive_turns_device (state->request_count as described there)
+ * A frame gd_receive_frames leaves GD_RECV_UNDECODED gets GD_TURN_NONE and touches no state.  Enqueue-only, but
+ * GD_ESTATE inside a hipGraph capture, as gd_receive_turns_device. */
+int gd_receive_turns_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                                   uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                                   const gd_frame_fields* d_out, const gd_frame_turn_fields* d_turn_out,
+                                   uint32_t* d_ctx, uint8_t* d_status, uint32_t* d_perm, uint32_t* d_offsets,
+                                   int64_t ttl_age_ticks, const uint8_t* d_msg_flags_or, const gd_turn_state* state,
+                                   uint8_t* d_turn, uint32_t* d_num_running_out, uint32_t* d_running_idx,
+                                   uint32_t* d_start_idx, uint32_t* d_n_start, uint32_t* d_wait_perm,
+                                   uint32_t* d_wait_offsets);
+/* Host pointers (state's and recv_limits' arrays too; out_n_start a host word); synchronous. */
+int gd_receive_turns_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                            uint32_t n_ctx, const gd_recv_limits* recv_limits, const gd_frame_fields* out,
+                            const gd_frame_turn_fields* turn_out, uint32_t* out_ctx, uint8_t* out_status,
+                            uint32_t* out_perm, uint32_t* out_offsets, int64_t ttl_age_ticks,
+                            const uint8_t* msg_flags_or, const gd_turn_state* state, uint8_t* out_turn,
+                            uint32_t* out_num_running, uint32_t* out_running_idx, uint32_t* out_start_idx,
+                            uint32_t* out_n_start, uint32_t* out_wait_perm, uint32_t* out_wait_offsets);
 
 /* ---- turn completion and message pump (Dispatcher.OnActivationCompletedRequest) ---------------------
  * The other half of the turn cycle: InvokeWorkItem.Execute's continuation (Scheduler/InvokeWorkItem.cs:50-55,

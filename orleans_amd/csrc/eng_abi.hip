@@ -163,6 +163,7 @@ void gd_destroy(gd_handle* h) {
     free_buf(h->ad_last);
     for (DevBuf& b : h->ad_buf) free_buf(b);
     for (DevBuf& b : h->fr_recv) free_buf(b);
+    for (DevBuf& b : h->frt_scr) free_buf(b);
     for (DevBuf& b : h->recv_scr) free_buf(b);
     for (auto& t : h->pending) {
         (void)hipEventDestroy(t.a);

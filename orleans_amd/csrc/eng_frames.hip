@@ -30,17 +30,29 @@ int check_frames_args(gd_handle* h, const void* buf, const void* off, uint32_t n
     return GD_OK;
 }
 
+// The struct of device pointers as the kernel takes it; all null = no turn field wanted.
+static FrameTurnFields frame_turn_fields(const gd_frame_turn_fields* t) {
+    if (!t) return FrameTurnFields{};
+    return FrameTurnFields{t->ttl, t->forward_count, t->msg_flags, t->result, t->rejection_type, t->resend_count};
+}
+
 int decode_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
-                         const gd_frame_fields* out, bool ext) {
+                         const gd_frame_fields* out, bool ext, const gd_frame_turn_fields* turn) {
     FrameFields ff = frame_fields(out);
+    const FrameTurnFields tf = frame_turn_fields(turn);
+    const bool want_turn = tf.ttl || tf.forward_count || tf.msg_flags || tf.result || tf.rejection_type || tf.resend_count;
     if (ext) {                          // where each TargetGrain's KeyExt string lies in buf
         GD_TRY(ensure(h, h->fr_ext[0], (size_t)n * 8 + 8));
         GD_TRY(ensure(h, h->fr_ext[1], (size_t)n * 4 + 4));
         ff.tg_ext_off = (uint64_t*)h->fr_ext[0].p;
         ff.tg_ext_len = (int32_t*)h->fr_ext[1].p;
     }
-    return launch(h, "k_decode_frames", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_decode_frames, buf, len, off, n,
-                  ff);
+    // the turn headers come out of the same walk; without them the kernel every other caller launches
+    if (want_turn)
+        return launch(h, "k_decode_frames_turn", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_decode_frames<true>, buf,
+                      len, off, n, ff, tf);
+    return launch(h, "k_decode_frames", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_decode_frames<false>, buf, len,
+                  off, n, ff, tf);
 }
 
 // ext: KeyExt targets (string-keyed grains) are routed too, their strings read from buf itself.
@@ -90,6 +102,31 @@ int frame_scratch(gd_handle* h, uint32_t n, const gd_frame_fields* want, gd_fram
     return GD_OK;
 }
 
+// The host-pointer outputs of a frame-fed call through the staging pool: 11 + 6 slots, one a member of the two
+// structs.  flags and target_grain are always held (the kernel writes them); a member not wanted stays null.
+void stage_frame_outputs(HostStage& io, uint32_t n, const gd_frame_fields* want, const gd_frame_turn_fields* twant,
+                         gd_frame_fields* dev, gd_frame_turn_fields* tdev) {
+    const gd_frame_fields w = want ? *want : gd_frame_fields{};
+    const gd_frame_turn_fields t = twant ? *twant : gd_frame_turn_fields{};
+    dev->flags = w.flags ? io.out(w.flags, n, 8) : io.hold<uint32_t>(n, 8);
+    dev->target_grain = w.target_grain ? io.out(w.target_grain, n, 8) : io.hold<gd_key>(n, 8);
+    dev->mask = io.out_if(w.mask, n, 8);
+    dev->target_activation = io.out_if(w.target_activation, n, 8);
+    dev->sending_activation = io.out_if(w.sending_activation, n, 8);
+    dev->sending_grain = io.out_if(w.sending_grain, n, 8);
+    dev->target_silo = io.out_if(w.target_silo, (size_t)n * 24, 8);
+    dev->sending_silo = io.out_if(w.sending_silo, (size_t)n * 24, 8);
+    dev->correlation_id = io.out_if(w.correlation_id, n, 8);
+    dev->category = io.out_if(w.category, n, 8);
+    dev->direction = io.out_if(w.direction, n, 8);
+    tdev->ttl = io.out_if(t.ttl, n, 8);
+    tdev->forward_count = io.out_if(t.forward_count, n, 8);
+    tdev->msg_flags = io.out_if(t.msg_flags, n, 8);
+    tdev->result = io.out_if(t.result, n, 8);
+    tdev->rejection_type = io.out_if(t.rejection_type, n, 8);
+    tdev->resend_count = io.out_if(t.resend_count, n, 8);
+}
+
 int frame_results(gd_handle* h, uint32_t n, const gd_frame_fields* want, const gd_frame_fields* dev) {
     if (!want) return GD_OK;
     const size_t sz[11] = {4, 24, 4, 24, 24, 24, 24, 24, 8, 1, 1};
@@ -108,6 +145,32 @@ int gd_decode_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len
                             uint32_t n, const gd_frame_fields* d_out) {
     GD_TRY(check_frames_args(h, d_buf, d_frame_off, n, d_out));
     return n ? decode_frames_device(h, d_buf, buf_len, d_frame_off, n, d_out) : GD_OK;
+}
+
+int gd_decode_frames_turn_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                                 uint32_t n, const gd_frame_fields* d_out, const gd_frame_turn_fields* d_turn_out) {
+    GD_TRY(check_frames_args(h, d_buf, d_frame_off, n, d_out));
+    if (d_turn_out && ((uintptr_t)d_turn_out->ttl & 7)) return set_err(h, GD_EINVAL, "ttl output must be 8-byte aligned");
+    if (d_turn_out && ((uintptr_t)d_turn_out->resend_count & 3))
+        return set_err(h, GD_EINVAL, "resend_count output must be 4-byte aligned");
+    return n ? decode_frames_device(h, d_buf, buf_len, d_frame_off, n, d_out, false, d_turn_out) : GD_OK;
+}
+
+int gd_decode_frames_turn(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                          const gd_frame_fields* out, const gd_frame_turn_fields* turn_out) {
+    GD_TRY(check_frames_args(h, buf, frame_off, n, out));
+    if (n == 0) return GD_OK;
+    HIP_TRY(h, hipSetDevice(h->device));
+    HostStage io(h);
+    const uint8_t* dbuf = io.in(buf, (size_t)buf_len);
+    const uint64_t* doff = io.in(frame_off, n);
+    gd_frame_fields dev{};
+    gd_frame_turn_fields tdev{};
+    stage_frame_outputs(io, n, out, turn_out, &dev, &tdev);
+    GD_TRY(io.status());
+    GD_TRY(decode_frames_device(h, dbuf, buf_len, doff, n, &dev, false, &tdev));
+    GD_TRY(io.fetch());
+    return sync(h);
 }
 
 int gd_decode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
@@ -220,7 +283,7 @@ AdArgs ad_args(gd_handle* h) { return AdArgs{h->ad_slots, h->ad_cap ? h->ad_cap 
 // -> ReceiveMessage -> bucketing.  Frames without a complete decoded address: RECV_UNDECODED.
 int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
                           uint32_t n_ctx, const gd_recv_limits* lim, const gd_frame_fields* out, uint32_t* ctx,
-                          uint8_t* st, uint32_t* perm, uint32_t* offsets) {
+                          uint8_t* st, uint32_t* perm, uint32_t* offsets, const gd_frame_turn_fields* turn) {
     gd_frame_fields o2 = *out;
     if (n) {
         if (!o2.target_activation) {
@@ -231,7 +294,7 @@ int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const 
             GD_TRY(ensure(h, h->fr_recv[1], (size_t)n + 8));
             o2.direction = (uint8_t*)h->fr_recv[1].p;
         }
-        GD_TRY(decode_frames_device(h, buf, len, off, n, &o2));
+        GD_TRY(decode_frames_device(h, buf, len, off, n, &o2, false, turn));
     }
     return receive_device(h, o2.target_grain, o2.target_activation, o2.direction, (const uint32_t*)o2.flags, n, n_ctx,
                           lim, ctx, st, perm, offsets);

@@ -31,10 +31,11 @@ int check_turn_args(gd_handle* h, const void* ta, const void* sa, bool fused, ui
     return GD_OK;
 }
 
-// The turn stage on device arrays (state's arrays device memory).
+// The turn stage on device arrays (state's arrays device memory).  adj: the frame-fed chain's ttl age and flag
+// merge, applied in the stage's own loads; the kernels without them run when there is nothing to apply.
 int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uint8_t* dir, const int64_t* ttl,
                  const uint8_t* fwd, const uint8_t* mf, const gd_key* ta, const gd_key* sa, uint32_t n, uint32_t n_ctx,
-                 const gd_turn_state* s, const TurnOut& o) {
+                 const gd_turn_state* s, const TurnOut& o, TurnFrameAdj adj = TurnFrameAdj{0, nullptr, nullptr}) {
     StageTime stage(h, "stage:turns");
     const dim3 gc(blocks_for(n_ctx, BLOCK)), bc(BLOCK);
     GD_TRY(launch(h, "k_turn_init", gc, bc, 0, k_turn_init, s->num_running, n_ctx, o.num_running, o.running_idx));
@@ -66,8 +67,16 @@ int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uin
         GD_TRY(ensure(h, h->turn_scr[5], (size_t)n * 4));
         wkey = (uint32_t*)h->turn_scr[5].p;
     }
-    GD_TRY(launch(h, "k_turn_classify", dim3(tiles), dim3(TN_NT), 0, k_turn_classify, ctx, rs, dir, ttl, fwd, mf,
-                  chain ? ta : nullptr, chain ? sa : nullptr, n, n_ctx, a, o.turn, o.running_idx, pkey));
+    const bool adjust = adj.ttl_age != 0 || adj.flags_or;
+    const uint8_t* mf_in = mf;      // what k_turn_classify loads
+    if (adj.flags_or) {             // k_turn_decide reads the Running message's flags: the merged ones, written once
+        GD_TRY(ensure(h, h->turn_scr[6], (size_t)n));
+        adj.flags_out = (uint8_t*)h->turn_scr[6].p;
+        mf = adj.flags_out;
+    }
+    GD_TRY(launch(h, "k_turn_classify", dim3(tiles), dim3(TN_NT), 0,
+                  adjust ? k_turn_classify<true> : k_turn_classify<false>, ctx, rs, dir, ttl, fwd, mf_in,
+                  chain ? ta : nullptr, chain ? sa : nullptr, n, n_ctx, a, o.turn, o.running_idx, pkey, adj));
     // each message's place among its context's participating messages: CheckOverloaded's count (gd_turns.h)
     if (limits) GD_TRY(bucket_device(h, pkey, n, n_ctx, (uint32_t*)h->turn_scr[2].p, roff, rank));
     GD_TRY(launch(h, "k_turn_decide", dim3(tiles), dim3(TN_NT), 0, k_turn_decide, ctx, mf, n, n_ctx, a,
@@ -81,6 +90,55 @@ int turns_device(gd_handle* h, const uint32_t* ctx, const uint8_t* rs, const uin
                       (const uint32_t*)tile_cnt, tiles, o.start_idx, n, o.n_start));
     }
     if (o.wait_perm) GD_TRY(bucket_device(h, wkey, n, n_ctx, o.wait_perm, o.wait_offsets));
+    return GD_OK;
+}
+
+// Frames -> decode (turn headers included) -> ReceiveMessage -> ReceiveRequest, all on the handle's stream.  What
+// the caller did not ask back is decoded into the handle's scratch; SendingActivation only when the call-chain
+// test reads it.
+int receive_turns_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
+                                uint32_t n_ctx, const gd_recv_limits* lim, const gd_frame_fields* out,
+                                const gd_frame_turn_fields* turn_out, uint32_t* ctx, uint8_t* st, uint32_t* perm,
+                                uint32_t* offsets, int64_t ttl_age, const uint8_t* flags_or, const gd_turn_state* s,
+                                const TurnOut& o) {
+    gd_frame_fields f = out ? *out : gd_frame_fields{};
+    gd_frame_turn_fields t = turn_out ? *turn_out : gd_frame_turn_fields{};
+    const bool chain = s->allow_call_chain_reentrancy != 0;
+    if (n) {
+        auto scratch = [&](auto*& p, int k, size_t elem) -> int {
+            if (p) return GD_OK;
+            GD_TRY(ensure(h, h->frt_scr[k], (size_t)n * elem + 8));
+            p = (std::remove_reference_t<decltype(p)>)h->frt_scr[k].p;
+            return GD_OK;
+        };
+        GD_TRY(scratch(f.flags, 0, 4));
+        GD_TRY(scratch(f.target_grain, 1, sizeof(gd_key)));
+        GD_TRY(scratch(f.target_activation, 2, sizeof(gd_key)));
+        if (chain) GD_TRY(scratch(f.sending_activation, 3, sizeof(gd_key)));
+        GD_TRY(scratch(f.direction, 4, 1));
+        GD_TRY(scratch(t.ttl, 5, 8));
+        GD_TRY(scratch(t.forward_count, 6, 1));
+        GD_TRY(scratch(t.msg_flags, 7, 1));
+    }
+    GD_TRY(receive_frames_device(h, buf, len, off, n, n_ctx, lim, &f, ctx, st, perm, offsets, &t));
+    return turns_device(h, ctx, st, f.direction, t.ttl, t.forward_count, t.msg_flags, f.target_activation,
+                        chain ? f.sending_activation : nullptr, n, n_ctx, s, o, TurnFrameAdj{ttl_age, flags_or, nullptr});
+}
+
+int check_turn_frames_args(gd_handle* h, const void* buf, const void* off, uint32_t n, uint32_t n_ctx,
+                           const gd_frame_fields* out, const gd_frame_turn_fields* turn_out, const void* ctx,
+                           const void* st, const void* perm, const void* offsets, int64_t ttl_age,
+                           const gd_turn_state* s, const TurnOut& o) {
+    GD_TRY(check_turn_args(h, nullptr, nullptr, true, n, n_ctx, s, o));
+    if (n && (!buf || !off || !ctx || !st)) return set_err(h, GD_EINVAL, "null argument");
+    if (out && n && (!out->flags || !out->target_grain))
+        return set_err(h, GD_EINVAL, "a frame-field struct needs flags and target_grain");
+    if (out && (((uintptr_t)out->target_silo | (uintptr_t)out->sending_silo) & 3))
+        return set_err(h, GD_EINVAL, "silo outputs must be 4-byte aligned");
+    if (turn_out && (((uintptr_t)turn_out->ttl & 7) || ((uintptr_t)turn_out->resend_count & 3)))
+        return set_err(h, GD_EINVAL, "ttl / resend_count outputs must be 8- / 4-byte aligned");
+    if ((perm != nullptr) != (offsets != nullptr)) return set_err(h, GD_EINVAL, "perm and offsets go together");
+    if (ttl_age < 0) return set_err(h, GD_EINVAL, "ttl_age_ticks < 0");
     return GD_OK;
 }
 
@@ -159,6 +217,74 @@ int gd_receive_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd
                           d_status, d_perm, d_offsets));
     return turns_device(h, d_ctx, d_status, d_direction, d_ttl, d_forward_count, d_msg_flags, d_target_activation,
                         d_sending_activation, n, n_ctx, state, o);
+}
+
+int gd_receive_turns_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                                   uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                                   const gd_frame_fields* d_out, const gd_frame_turn_fields* d_turn_out,
+                                   uint32_t* d_ctx, uint8_t* d_status, uint32_t* d_perm, uint32_t* d_offsets,
+                                   int64_t ttl_age_ticks, const uint8_t* d_msg_flags_or, const gd_turn_state* state,
+                                   uint8_t* d_turn, uint32_t* d_num_running_out, uint32_t* d_running_idx,
+                                   uint32_t* d_start_idx, uint32_t* d_n_start, uint32_t* d_wait_perm,
+                                   uint32_t* d_wait_offsets) {
+    const TurnOut o{d_turn, d_num_running_out, d_running_idx, d_start_idx, d_n_start, d_wait_perm, d_wait_offsets};
+    GD_TRY(check_turn_frames_args(h, d_buf, d_frame_off, n, n_ctx, d_out, d_turn_out, d_ctx, d_status, d_perm,
+                                  d_offsets, ttl_age_ticks, state, o));
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_receive_turns_frames_device"));
+    return receive_turns_frames_device(h, d_buf, buf_len, d_frame_off, n, n_ctx, recv_limits, d_out, d_turn_out, d_ctx,
+                                       d_status, d_perm, d_offsets, ttl_age_ticks, d_msg_flags_or, state, o);
+}
+
+int gd_receive_turns_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                            uint32_t n_ctx, const gd_recv_limits* recv_limits, const gd_frame_fields* out,
+                            const gd_frame_turn_fields* turn_out, uint32_t* out_ctx, uint8_t* out_status,
+                            uint32_t* out_perm, uint32_t* out_offsets, int64_t ttl_age_ticks,
+                            const uint8_t* msg_flags_or, const gd_turn_state* state, uint8_t* out_turn,
+                            uint32_t* out_num_running, uint32_t* out_running_idx, uint32_t* out_start_idx,
+                            uint32_t* out_n_start, uint32_t* out_wait_perm, uint32_t* out_wait_offsets) {
+    const TurnOut ho{out_turn, out_num_running, out_running_idx, out_start_idx, out_n_start, out_wait_perm,
+                     out_wait_offsets};
+    GD_TRY(check_turn_frames_args(h, buf, frame_off, n, n_ctx, out, turn_out, out_ctx, out_status, out_perm, out_offsets,
+                                  ttl_age_ticks, state, ho));
+    HIP_TRY(h, hipSetDevice(h->device));
+    GD_TRY(check_not_capturing(h, "gd_receive_turns_frames"));
+    HostStage io(h);
+    const uint8_t* dbuf = io.in(buf, n ? (size_t)buf_len : 0);
+    const uint64_t* doff = io.in(frame_off, n);
+    gd_recv_limits dl{};
+    const gd_recv_limits* pl = nullptr;
+    const uint32_t* drc = io.in(recv_limits ? recv_limits->request_count : nullptr, n_ctx);
+    if (drc) {
+        dl = *recv_limits;
+        dl.request_count = drc;
+        pl = &dl;
+    }
+    gd_frame_fields dev{};
+    gd_frame_turn_fields tdev{};
+    stage_frame_outputs(io, n, out, turn_out, &dev, &tdev);
+    uint32_t* dctx = io.out(out_ctx, n, 8);
+    uint8_t* dst = io.out(out_status, n, 8);
+    uint32_t* dperm = io.out_if(out_perm, n, 8);
+    uint32_t* doffs = io.out_if(out_offsets, (size_t)n_ctx + 3);
+    const uint8_t* dmor = io.in(msg_flags_or, n);
+    gd_turn_state ds = *state;
+    ds.ctx_flags = io.in(state->ctx_flags, n_ctx);
+    ds.num_running = io.in(state->num_running, n_ctx);
+    ds.request_count = io.in(state->request_count, n_ctx);
+    TurnOut o;
+    o.turn = io.out(out_turn, n, 16);
+    o.num_running = io.out(out_num_running, n_ctx, 4);
+    o.running_idx = io.out(out_running_idx, n_ctx, 4);
+    o.start_idx = io.out_if(out_start_idx, n, 4);
+    o.n_start = io.out_if(out_n_start, 1);
+    o.wait_perm = io.out_if(out_wait_perm, n, 4);
+    o.wait_offsets = io.out_if(out_wait_offsets, (size_t)n_ctx + 2);
+    GD_TRY(io.status());
+    GD_TRY(receive_turns_frames_device(h, dbuf, buf_len, doff, n, n_ctx, pl, &dev, &tdev, dctx, dst, dperm, doffs,
+                                       ttl_age_ticks, dmor, &ds, o));
+    GD_TRY(io.fetch());
+    return sync_checked(h);
 }
 
 }  // extern "C"

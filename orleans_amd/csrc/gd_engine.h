@@ -143,6 +143,7 @@ struct gd_handle {
     DevBuf ad_last;
     DevBuf ad_buf[8];
     DevBuf fr_recv[3];                // frames: TargetActivation / Direction scratch when the caller wants neither
+    DevBuf frt_scr[8];                // gd_receive_turns_frames*: the decoded fields the caller did not ask back
     DevBuf recv_scr[2];               // receive with limits but no buckets wanted: perm / offsets scratch
 
     // sender queues (gd_sendq.h, eng_send.hip): the per-silo application bucket (gd_send_configure)
@@ -158,7 +159,7 @@ struct gd_handle {
     DevBuf place_scr[7];              // tile counts, block counts; candidates' idx, keys, vals, winners, inserted
 
     // turn admission (gd_turns.h, eng_turns.hip)
-    DevBuf turn_scr[6];               // tile counts; rank key, perm, offsets, rank (limits); wait-list key
+    DevBuf turn_scr[7];               // tile counts; rank key, perm, offsets, rank (limits); wait-list key; merged flags
 
     // turn completion and message pump, wait-list merge (gd_pump.h, eng_pump.hip)
     DevBuf pump_scr[6];               // completions' perm, offsets; start counts, first positions; work list, its count
@@ -211,11 +212,11 @@ struct gd_handle {
     DevBuf cls_wide, cls_silo;
 
     // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
-    // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_turns).
+    // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_receive_turns_frames).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads
     // what an earlier one staged; a call that returned early on an error left its work on the same stream,
     // ahead of the next call's, and ensure() synchronises before it frees a slot to grow it.
-    static constexpr uint32_t STAGE_SLOTS = 18;
+    static constexpr uint32_t STAGE_SLOTS = 36;
     DevBuf stage_buf[STAGE_SLOTS];
 
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
@@ -523,7 +524,10 @@ int merge_core(gd_handle* h, const gd_key* dk, const gd_val* dvals, const int32_
 AdArgs ad_args(gd_handle* h);
 int check_frames_args(gd_handle* h, const void* buf, const void* off, uint32_t n, const gd_frame_fields* out);
 int decode_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
-                         const gd_frame_fields* out, bool ext = false);
+                         const gd_frame_fields* out, bool ext = false, const gd_frame_turn_fields* turn = nullptr);
+struct HostStage;
+void stage_frame_outputs(HostStage& io, uint32_t n, const gd_frame_fields* want, const gd_frame_turn_fields* twant,
+                         gd_frame_fields* dev, gd_frame_turn_fields* tdev);
 int frame_scratch(gd_handle* h, uint32_t n, const gd_frame_fields* want, gd_frame_fields* dev);
 int frame_results(gd_handle* h, uint32_t n, const gd_frame_fields* want, const gd_frame_fields* dev);
 int bucket_lsd(gd_handle* h, const uint32_t* acts, uint32_t n, uint32_t n_act, uint32_t* perm, uint32_t* offsets,
@@ -539,7 +543,7 @@ int receive_device(gd_handle* h, const gd_key* tg, const gd_key* ta, const uint8
                    uint32_t* offsets);
 int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, uint32_t n,
                           uint32_t n_ctx, const gd_recv_limits* lim, const gd_frame_fields* out, uint32_t* ctx,
-                          uint8_t* st, uint32_t* perm, uint32_t* offsets);
+                          uint8_t* st, uint32_t* perm, uint32_t* offsets, const gd_frame_turn_fields* turn = nullptr);
 int grow(gd_handle* h, DevBuf& b, size_t bytes);
 int comm_setup(gd_handle* h);
 int kx_rehash(gd_handle* h, uint64_t cap);

@@ -59,6 +59,19 @@ struct FrameFields {   // device pointers; nullptr = field not wanted (flags and
     int32_t* tg_ext_len;           //   and UTF-8 length (-1 null, GD_KEYEXT_HOST: no target decoded)
 };
 
+// The turn-admission headers of the same walk (gd_frame_turn_fields); nullptr = field not wanted.
+struct FrameTurnFields {
+    int64_t* ttl;                  // TimeToLive ticks as written, GD_TTL_NONE when absent
+    uint8_t* forward_count;        // ForwardCount clamped to [0, 255]
+    uint8_t* msg_flags;            // GD_MSG_READ_ONLY | GD_MSG_ALWAYS_INTERLEAVE from the two bool tokens
+    uint8_t* result;
+    uint8_t* rejection_type;
+    int32_t* resend_count;
+};
+
+constexpr uint32_t TOKEN_TRUE = 3;                // SerializationTokenType.True: ReadBool is token == True
+constexpr uint32_t FT_READ_ONLY = 1u, FT_ALWAYS_INTERLEAVE = 2u;   // GD_MSG_*
+
 // Byte cursor over one frame: LDS window first, global memory past it.
 struct FrameCursor {
     const uint32_t* row;   // LDS row of this frame (dword aligned at frame_start & ~3)
@@ -142,9 +155,12 @@ __device__ __forceinline__ void store_silo(uint32_t* out, uint32_t i, const uint
     for (int j = 0; j < 6; ++j) out[6ull * i + j] = s[j];
 }
 
+// TURN: the turn-admission headers (FrameTurnFields t) come out of the same walk; without it the walk steps
+// over their bytes and t is never read.
+template <bool TURN>
 static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                          const uint64_t* __restrict__ frame_off, uint32_t n,
-                                                         FrameFields o) {
+                                                         FrameFields o, FrameTurnFields t) {
     __shared__ uint32_t s_win[BLOCK / WAVE][WAVE][FRAME_ROW];
     const uint32_t lane = threadIdx.x & (WAVE - 1), w = threadIdx.x / WAVE;
     const uint32_t base = blockIdx.x * BLOCK + w * WAVE;
@@ -190,6 +206,10 @@ static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* _
     int32_t tg_ext = GD_KEYEXT_HOST;
     uint64_t tg_ext_off = 0;
     uint32_t ts[6] = {0, 0, 0, 0, 0, 0}, ss[6] = {0, 0, 0, 0, 0, 0};
+    // TURN only (dead otherwise)
+    int64_t ttl = GD_TTL_NONE;
+    int32_t fwd = 0, resend = 0;
+    uint32_t mf = 0, res = 0, rej = 0;
 
     const uint64_t a0 = start & ~3ull;
     // staged bytes = the whole 16-B chunks of the window that lie below dw_end
@@ -225,18 +245,25 @@ static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* _
             if ((m & H_CATEGORY) && hw.take(1)) cat = hw.c.u8(hw.p - 1);
             if (m & H_DEBUG_CONTEXT) hw.skip_string();
             if ((m & H_DIRECTION) && !hw.bad && hw.take(1)) dir = hw.c.u8(hw.p - 1);
-            if (m & H_TIME_TO_LIVE) hw.take(8);
-            if (m & H_FORWARD_COUNT) hw.take(4);
+            if ((m & H_TIME_TO_LIVE) && hw.take(8) && TURN) ttl = (int64_t)hw.c.u64(hw.p - 8);
+            if ((m & H_FORWARD_COUNT) && hw.take(4) && TURN) fwd = (int32_t)hw.c.u32(hw.p - 4);
             if (m & H_GENERIC_GRAIN_TYPE) hw.skip_string();
             if ((m & H_CORRELATION_ID) && !hw.bad && hw.take(8)) corr = (int64_t)hw.c.u64(hw.p - 8);
             // bool tokens: 1 byte each
             const uint32_t nb = __popc(m & (H_ALWAYS_INTERLEAVE | H_IS_NEW_PLACEMENT | H_READ_ONLY | H_IS_UNORDERED));
-            if (nb) hw.take(nb);
+            if (nb && hw.take(nb) && TURN) {
+                // Serializer order: AlwaysInterleave, IsNewPlacement, ReadOnly, IsUnordered
+                const uint32_t b0 = hw.p - nb;
+                if ((m & H_ALWAYS_INTERLEAVE) && hw.c.u8(b0) == TOKEN_TRUE) mf |= FT_ALWAYS_INTERLEAVE;
+                if ((m & H_READ_ONLY) &&
+                    hw.c.u8(b0 + __popc(m & (H_ALWAYS_INTERLEAVE | H_IS_NEW_PLACEMENT))) == TOKEN_TRUE)
+                    mf |= FT_READ_ONLY;
+            }
             if (m & H_NEW_GRAIN_TYPE) hw.skip_string();
             if (m & H_REJECTION_INFO) hw.skip_string();
-            if (m & H_REJECTION_TYPE) hw.take(1);
-            if (m & H_RESEND_COUNT) hw.take(4);
-            if (m & H_RESULT) hw.take(1);
+            if ((m & H_REJECTION_TYPE) && hw.take(1) && TURN) rej = hw.c.u8(hw.p - 1);
+            if ((m & H_RESEND_COUNT) && hw.take(4) && TURN) resend = (int32_t)hw.c.u32(hw.p - 4);
+            if ((m & H_RESULT) && hw.take(1) && TURN) res = hw.c.u8(hw.p - 1);
             if (m & H_SENDING_ACTIVATION) sa = hw.key(nullptr);
             if (m & H_SENDING_GRAIN) sg = hw.key(nullptr);
             if ((m & H_SENDING_SILO) && !hw.bad && hw.take(24)) {
@@ -272,6 +299,19 @@ static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* _
         tg_ext = GD_KEYEXT_HOST;
 #pragma unroll
         for (int j = 0; j < 6; ++j) ts[j] = ss[j] = 0;
+    }
+    if (TURN) {
+        if (malformed) {
+            ttl = GD_TTL_NONE;
+            fwd = resend = 0;
+            mf = res = rej = 0;
+        }
+        if (t.ttl) t.ttl[i] = ttl;
+        if (t.forward_count) t.forward_count[i] = (uint8_t)(fwd < 0 ? 0 : (fwd > 255 ? 255 : fwd));
+        if (t.msg_flags) t.msg_flags[i] = (uint8_t)mf;
+        if (t.result) t.result[i] = (uint8_t)res;
+        if (t.rejection_type) t.rejection_type[i] = (uint8_t)rej;
+        if (t.resend_count) t.resend_count[i] = resend;
     }
     o.flags[i] = flags;
     store_key(o.target_grain, i, tg);

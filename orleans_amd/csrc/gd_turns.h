@@ -111,8 +111,17 @@ __device__ __forceinline__ bool turn_same_key(const gd_key* __restrict__ a, cons
     return pa[1] == pb[1] && pa[0] == pb[0] && pa[2] == pb[2];   // N1 differs first between activations
 }
 
+// The frame-fed chain's adjustments, applied where the turn stage loads a message (no pass of their own): the
+// decoder wrote the ttl and the flags as the wire has them.
+struct TurnFrameAdj {
+    int64_t ttl_age;                // Message.TimeToLive's getter: wire ttl - (UtcNow - _localCreationTime), ticks >= 0
+    const uint8_t* flags_or;        // OR-ed into the decoded flags (GD_MSG_MAY_INTERLEAVE comes from C#); may be null
+    uint8_t* flags_out;             // with flags_or: the merged flags, for k_turn_decide's read of the Running message's
+};
+
 // Item (w, r, lane) of a tile <-> message base + (w * TN_IT + r) * 64 + lane: a wave row is 64 consecutive
-// messages, lanes in arrival order.
+// messages, lanes in arrival order.  ADJ: adj is applied (the instantiation without it never reads it).
+template <bool ADJ>
 static __global__ void __launch_bounds__(TN_NT) k_turn_classify(const uint32_t* __restrict__ ctx,
                                                          const uint8_t* __restrict__ rs,
                                                          const uint8_t* __restrict__ dir,
@@ -122,7 +131,7 @@ static __global__ void __launch_bounds__(TN_NT) k_turn_classify(const uint32_t* 
                                                          const gd_key* __restrict__ ta, const gd_key* __restrict__ sa,
                                                          uint32_t n, uint32_t n_ctx, TurnArgs a,
                                                          uint8_t* __restrict__ turn, uint32_t* __restrict__ first,
-                                                         uint32_t* __restrict__ pkey) {
+                                                         uint32_t* __restrict__ pkey, TurnFrameAdj adj) {
     const uint32_t base = blockIdx.x * TN_TILE;
     const uint32_t lane = lane_id(), w = threadIdx.x / WAVE;
     // every streamed load of the thread before the first use (one wait, not one per message)
@@ -137,6 +146,11 @@ static __global__ void __launch_bounds__(TN_NT) k_turn_classify(const uint32_t* 
         tv[r] = ttl ? ttl[li] : GD_TTL_NONE;
         fv[r] = fwd ? (uint32_t)fwd[li] : 0u;
         mv[r] = mflags ? (uint32_t)mflags[li] : 0u;
+        if (ADJ) {
+            if (adj.flags_or) mv[r] |= (uint32_t)adj.flags_or[li];
+            // a ttl with a value ages, saturating at INT64_MIN (ttl_age >= 0: it can only fall)
+            if (tv[r] != GD_TTL_NONE) tv[r] = tv[r] < INT64_MIN + adj.ttl_age ? INT64_MIN : tv[r] - adj.ttl_age;
+        }
     }
     uint32_t hot_key = NONE32;                          // wave-uniform: the context of the wave's first atomic
 #pragma unroll
@@ -183,6 +197,7 @@ static __global__ void __launch_bounds__(TN_NT) k_turn_classify(const uint32_t* 
         if (i < n) {
             turn[i] = (uint8_t)t;
             if (pkey) pkey[i] = part ? c : n_ctx;
+            if (ADJ && adj.flags_out) adj.flags_out[i] = (uint8_t)mv[r];
         }
         // The word only ever falls, so a (possibly stale) read that is already below i makes the atomic
         // redundant: a hot context takes atomics from the waves in flight when the batch starts, not from

@@ -89,6 +89,8 @@ EXPORTED_SYMBOLS = [
     "gd_place_configure", "gd_route_place_device", "gd_route_place", "gd_route_place_bucket_device",
     "gd_route_place_bucket",
     "gd_turns_device", "gd_turns", "gd_receive_turns_device",
+    "gd_decode_frames_turn_device", "gd_decode_frames_turn", "gd_receive_turns_frames_device",
+    "gd_receive_turns_frames",
     "gd_turns_complete_device", "gd_turns_complete", "gd_wait_list_merge_device", "gd_wait_list_merge",
     "gd_callbacks_configure", "gd_callbacks_clear", "gd_callbacks_count", "gd_callbacks_add_device",
     "gd_callbacks_add", "gd_callbacks_set_target_device", "gd_callbacks_set_target", "gd_callbacks_lookup_device",
@@ -165,6 +167,16 @@ FRAME_FIELDS = {"flags": (np.uint32, ()), "target_grain": (np.uint64, (3,)), "ma
                 "sending_grain": (np.uint64, (3,)), "target_silo": (np.uint8, (24,)),
                 "sending_silo": (np.uint8, (24,)), "correlation_id": (np.int64, ()),
                 "category": (np.uint8, ()), "direction": (np.uint8, ())}
+
+
+class gd_frame_turn_fields(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in
+                ("ttl", "forward_count", "msg_flags", "result", "rejection_type", "resend_count")]
+
+
+# gd_frame_turn_fields member -> numpy dtype of the host arrays
+FRAME_TURN_FIELDS = {"ttl": np.int64, "forward_count": np.uint8, "msg_flags": np.uint8, "result": np.uint8,
+                     "rejection_type": np.uint8, "resend_count": np.int32}
 
 
 class gd_multi_result(C.Structure):
@@ -372,6 +384,16 @@ def _load() -> C.CDLL:
         "gd_turns": (C.c_int, [P] + [P] * 8 + [U32, U32, C.POINTER(gd_turn_state)] + [P] * 7),
         "gd_receive_turns_device": (C.c_int, [P, P, P, P, U32, U32, C.POINTER(gd_recv_limits), P, P, P, P, P, P, P, P,
                                               C.POINTER(gd_turn_state)] + [P] * 7),
+        "gd_decode_frames_turn_device": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_frame_fields),
+                                                   C.POINTER(gd_frame_turn_fields)]),
+        "gd_decode_frames_turn": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_frame_fields),
+                                            C.POINTER(gd_frame_turn_fields)]),
+        "gd_receive_turns_frames_device": (C.c_int, [P, P, U64, P, U32, U32, C.POINTER(gd_recv_limits),
+                                                     C.POINTER(gd_frame_fields), C.POINTER(gd_frame_turn_fields),
+                                                     P, P, P, P, C.c_int64, P, C.POINTER(gd_turn_state)] + [P] * 7),
+        "gd_receive_turns_frames": (C.c_int, [P, P, U64, P, U32, U32, C.POINTER(gd_recv_limits),
+                                              C.POINTER(gd_frame_fields), C.POINTER(gd_frame_turn_fields),
+                                              P, P, P, P, C.c_int64, P, C.POINTER(gd_turn_state)] + [P] * 7),
         "gd_turns_complete_device": (C.c_int, [P, P, P, U32, U32, P, P, C.POINTER(gd_wait_list), U32] + [P] * 8),
         "gd_turns_complete": (C.c_int, [P, P, P, U32, U32, P, P, C.POINTER(gd_wait_list), U32] + [P] * 8),
         "gd_wait_list_merge_device": (C.c_int, [P, C.POINTER(gd_wait_list), P, U32, P, P, U32, P, U32, P, P, P, C.c_int,
@@ -1084,6 +1106,86 @@ class GrainDispatch:
                                             V(d_sending_activation), C.byref(state), V(d_turn), V(d_num_running_out),
                                             V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm),
                                             V(d_wait_offsets)))
+
+    # -- the frame-fed chain: receive buffer -> decode -> ReceiveMessage -> ReceiveRequest ----------
+    @staticmethod
+    def _frame_turn_host(n: int, turn_fields) -> Tuple[dict, Optional[gd_frame_turn_fields]]:
+        """turn_fields: None = no struct (NULL), else the members wanted (an empty list: a struct of NULLs)."""
+        if turn_fields is None:
+            return {}, None
+        arrs = {k: np.zeros(n, dtype=FRAME_TURN_FIELDS[k]) for k in turn_fields}
+        return arrs, gd_frame_turn_fields(**{k: (_ptr(a) if n else None) for k, a in arrs.items()})
+
+    def decode_frames_turn(self, buf: bytes, offsets, fields: Optional[Iterable[str]] = None,
+                           turn_fields: Optional[Iterable[str]] = tuple(FRAME_TURN_FIELDS)):
+        """gd_decode_frames_turn: (decoded fields, decoded turn headers), dicts of numpy arrays named like
+        gd_frame_fields / gd_frame_turn_fields.  turn_fields None passes a NULL struct."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        arrs, ff = self._frame_host(n, fields)
+        tarrs, tf = self._frame_turn_host(n, turn_fields)
+        self._c(lib.gd_decode_frames_turn(self.h, _ptr(b), len(buf), _ptr(off), n, C.byref(ff),
+                                          None if tf is None else C.byref(tf)))
+        return arrs, tarrs
+
+    def decode_frames_turn_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, d_fields: dict,
+                                  d_turn_fields: Optional[dict]):
+        ff = gd_frame_fields(**{k: C.c_void_p(v) for k, v in d_fields.items()})
+        tf = None if d_turn_fields is None else gd_frame_turn_fields(**{k: C.c_void_p(v)
+                                                                        for k, v in d_turn_fields.items()})
+        self._c(lib.gd_decode_frames_turn_device(self.h, C.c_void_p(d_buf), buf_len, C.c_void_p(d_offsets), n,
+                                                 C.byref(ff), None if tf is None else C.byref(tf)))
+
+    def receive_turns_frames(self, buf: bytes, offsets, n_ctx: int, ctx_flags, num_running, request_count,
+                             recv_request_count=None, recv_hard_limit: int = 0, recv_hard_limit_sw: int = 0,
+                             ttl_age_ticks: int = 0, msg_flags_or=None, hard_limit: int = 0, hard_limit_sw: int = 0,
+                             max_forward_count: int = 2, chain: bool = False, fields: Optional[Iterable[str]] = (),
+                             turn_fields: Optional[Iterable[str]] = ()):
+        """gd_receive_turns_frames: (decoded fields, decoded turn headers, ctx u32, status u8, perm u32,
+        offsets u32[n_ctx + 3], turn u8, num_running_out u32[n_ctx], running_idx u32[n_ctx],
+        start_idx u32[n_start], wait_perm u32[n], wait_offsets u32[n_ctx + 2])."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        arrs, ff = self._frame_host(n, fields)
+        tarrs, tf = self._frame_turn_host(n, turn_fields)
+        lim, keep = self._limits(recv_request_count, recv_hard_limit, recv_hard_limit_sw)
+        mor = self._opt(msg_flags_or, np.uint8)
+        fl, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        rc = self._opt(request_count, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        st = gd_turn_state(p(fl), p(nr), p(rc), hard_limit, hard_limit_sw, max_forward_count, int(chain))
+        ctx, rst = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        perm, offs = np.zeros(n, np.uint32), np.zeros(n_ctx + 3, np.uint32)
+        turn, nro, run = np.zeros(n, np.uint8), np.zeros(n_ctx, np.uint32), np.zeros(n_ctx, np.uint32)
+        start, n_start = np.zeros(max(n, 1), np.uint32), np.zeros(1, np.uint32)
+        wperm, woff = np.zeros(n, np.uint32), np.zeros(n_ctx + 2, np.uint32)
+        self._c(lib.gd_receive_turns_frames(self.h, _ptr(b), len(buf), _ptr(off), n, n_ctx,
+                                            None if lim is None else C.byref(lim), C.byref(ff),
+                                            None if tf is None else C.byref(tf), _ptr(ctx), _ptr(rst), _ptr(perm),
+                                            _ptr(offs), ttl_age_ticks, p(mor), C.byref(st), _ptr(turn), _ptr(nro),
+                                            _ptr(run), _ptr(start), _ptr(n_start), _ptr(wperm), _ptr(woff)))
+        return (arrs, tarrs, ctx, rst, perm, offs, turn, nro, run, start[:int(n_start[0])].copy(), wperm, woff)
+
+    def receive_turns_frames_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, n_ctx: int,
+                                    d_fields: Optional[dict], d_turn_fields: Optional[dict], d_ctx: int, d_status: int,
+                                    d_perm: Optional[int], d_offs: Optional[int], ttl_age_ticks: int,
+                                    d_msg_flags_or: Optional[int], state: gd_turn_state, d_turn: int,
+                                    d_num_running_out: int, d_running_idx: int, d_start_idx: Optional[int] = None,
+                                    d_n_start: Optional[int] = None, d_wait_perm: Optional[int] = None,
+                                    d_wait_offsets: Optional[int] = None, d_recv_request_count: Optional[int] = None,
+                                    recv_hard_limit: int = 0, recv_hard_limit_sw: int = 0):
+        V = lambda x: C.c_void_p(x or 0)
+        ff = None if d_fields is None else gd_frame_fields(**{k: C.c_void_p(v) for k, v in d_fields.items()})
+        tf = None if d_turn_fields is None else gd_frame_turn_fields(**{k: C.c_void_p(v)
+                                                                        for k, v in d_turn_fields.items()})
+        lim = gd_recv_limits(d_recv_request_count, recv_hard_limit, recv_hard_limit_sw) if d_recv_request_count else None
+        self._c(lib.gd_receive_turns_frames_device(
+            self.h, V(d_buf), buf_len, V(d_offsets), n, n_ctx, None if lim is None else C.byref(lim),
+            None if ff is None else C.byref(ff), None if tf is None else C.byref(tf), V(d_ctx), V(d_status), V(d_perm),
+            V(d_offs), ttl_age_ticks, V(d_msg_flags_or), C.byref(state), V(d_turn), V(d_num_running_out),
+            V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm), V(d_wait_offsets)))
 
     # -- turn completion and message pump (Dispatcher.OnActivationCompletedRequest) ---------------
     def turns_complete(self, done_ctx, n_ctx: int, ctx_flags, num_running, wait_offsets, wait_flags, done_flags=None,
