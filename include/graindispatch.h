@@ -2160,6 +2160,103 @@ int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const u
                      const uint32_t* new_type, const uint32_t* order, uint8_t* out_buf, uint64_t out_cap,
                      uint64_t* out_off, uint8_t* enc_status, uint64_t* out_total);
 
+/* ---- response writer: CreateResponseMessage / CreateRejectionResponse + Serialize for a batch ----
+ * The answer to a request is built by MessageFactory.CreateResponseMessage (MessageFactory.cs:49-100, from
+ * Dispatcher.SendResponse, Dispatcher.cs:769-783) or CreateRejectionResponse (:102-111, from
+ * Dispatcher.RejectMessage :203-222, IncomingMessageAgent.cs:104, MessageCenter.SendRejection :193-197) and then
+ * serialized (Message.cs:481-516).  Here the request frames are read where the receive stages left them and the
+ * answers are written as frames, output frame j answering input frame order[j].
+ *   kind[i]: GD_RSP_NONE (no answer), GD_RSP_RESPONSE (result[i]: 0 Success, 1 Error) or GD_RSP_REJECTION
+ *   (rejection_type[i]: Message.RejectionTypes, 0 Transient, 1 Overloaded, 3 Unrecoverable ...; info[i]: an index
+ *   into gd_respond_configure's strings, GD_RSP_NO_INFO or any index >= n_info: none).  Any other kind is NONE.
+ * For a request with mask m the answer's header is written in HeadersContainer.Serializer order (Message.cs:
+ * 1126-1244) with the mask GetHeadersMask (:1075-1117) gives for the message CreateResponseMessage builds:
+ *   Category         copied when the request has it and the byte is not 0 (the enum default)
+ *   DebugContext     copied when present with length > 0 (String.IsNullOrEmpty)
+ *   Direction        always, byte 1 (Response)
+ *   TimeToLive, CorrelationId   copied when present
+ *   AlwaysInterleave, ReadOnly  bit set and a True token (3) written only when the request's token is 3; a request
+ *                    carrying the bit with any other token loses it
+ *   RejectionInfo    kind REJECTION and info[i] names a non-empty string: int32 length + bytes
+ *   RejectionType    kind REJECTION and type != 0: one byte (Transient is the enum default: absent)
+ *   Result           byte 2 for a rejection, byte 1 for result[i] == 1, absent for Success
+ *   SendingActivation / SendingGrain / SendingSilo = the request's TargetActivation / TargetGrain / TargetSilo,
+ *                    each with its KeyExt string bytes as they stand; SendingActivation only when TargetGrain is
+ *                    present
+ *   TargetActivation / TargetGrain / TargetSilo = the request's SendingActivation / SendingGrain / SendingSilo;
+ *                    TargetActivation only when SendingGrain is present
+ *   TransactionInfo  the request's bytes from the end of its last sized field to the end of the header, when the
+ *                    bit is set
+ *   dropped          ForwardCount, ResendCount, GenericGrainType, NewGrainType, IsNewPlacement, IsUnordered,
+ *                    TargetObserver, the request's own RejectionInfo / RejectionType / Result and RequestContext,
+ *                    the mask-only bits 25, 26 and 28, and bytes behind the last field of a header without
+ *                    TransactionInfo
+ * headerLength is recomputed; bodyLength is the supplied body's length: the body of answer i is
+ * body[body_off[i] .. body_off[i + 1]) (body_off: n + 1 non-decreasing entries), copied as given -- the library
+ * invents no body bytes, the caller serializes the Response object or the null exception.
+ * RequestContextExtensions.Export is the responding thread's ambient context: a caller with a non-empty one keeps
+ * C# for that message (kind NONE).
+ * Status, one byte per input frame, decided in this order:
+ *   kind NONE                                                    -> GD_RSPST_SKIPPED
+ *   the decoder's GD_FRAME_MALFORMED length conditions           -> GD_RSPST_MALFORMED
+ *   CacheInvalidationHeader present (object-serialized ahead of Direction, which cannot then be read)
+ *                                                                -> GD_RSPST_FALLBACK
+ *   the walk to Direction runs off the header                    -> GD_RSPST_MALFORMED
+ *   the request's Direction byte present and != 0 (RejectMessage :209-221; a frame without Direction counts as a
+ *     request)                                                   -> GD_RSPST_DISCARDED
+ *   RequestContext present, or TargetObserver and TransactionInfo both present
+ *                                                                -> GD_RSPST_FALLBACK
+ *   the walk through TargetGrain runs off the header             -> GD_RSPST_MALFORMED
+ *   TargetGrain a system target (UniqueKey category 1) without TargetActivation: the answer needs
+ *     ActivationId.GetSystemActivation (MessageFactory.cs:79-82) -> GD_RSPST_FALLBACK
+ *   the rest of the walk runs off the header                     -> GD_RSPST_MALFORMED
+ *   else                                                         -> GD_RSPST_OK
+ * Only OK frames contribute bytes.  order, out_off[n + 1], out_cap, GD_EFULL (nothing written, out_off still
+ * complete, the handle's device error word) and n == 0 are gd_encode_frames*'s.  Totals are 32-bit: a call whose
+ * bound buf_len + body bytes + n * (16 + longest info string) reaches 2^32 is refused with GD_EINVAL; the device
+ * form cannot see the body bytes, checks the rest and leaves body_off[n] to the caller.  d_result,
+ * d_rejection_type, d_info, d_body / d_body_off (a pair) and d_order may each be NULL: Success, Transient, no
+ * info, empty bodies, batch order.  Frames must be disjoint ranges of buf.
+ * gd_respond_configure installs the RejectionInfo strings (the reference's hold Message.ToString() and exception
+ * text and cannot be reproduced: the caller picks one by index, as for NewGrainType).  It may be repeated (n_info
+ * may be 0) and synchronises the handle first; info_off[0] = 0, n_info + 1 non-decreasing entries.
+ * gd_respond_frames* returns GD_ESTATE before it, and inside a hipGraph capture.
+ * gd_respond_kinds*: kind / rejection type from the turn and receive statuses: GD_TURN_REJECT_OVERLOADED ->
+ * REJECTION, Overloaded (1); GD_TURN_REJECT_TRANSIENT -> REJECTION, Transient (0); else, with recv_status given,
+ * GD_RECV_REJECT_UNKNOWN -> REJECTION, Unrecoverable (3); GD_RECV_REJECT_OVERLOADED -> REJECTION, Overloaded (1);
+ * anything else NONE (type 0).  recv_status may be NULL.
+ * gd_silo_index*: wire24 holds n 24-byte wire SiloAddresses (ip[16], port, generation; 4-byte aligned, e.g.
+ * gd_frame_fields.sending_silo); silo[i] = the lowest index of that address in gd_encode_configure's table,
+ * GD_NO_SILO when it is not there.  GD_ESTATE before gd_encode_configure.  Its output feeds gd_send_queues*,
+ * whose perm is then `order` here: each sender queue's answers are one contiguous byte run. */
+#define GD_RSP_NONE      0
+#define GD_RSP_RESPONSE  1
+#define GD_RSP_REJECTION 2
+#define GD_RSPST_OK        0
+#define GD_RSPST_SKIPPED   1
+#define GD_RSPST_MALFORMED 2
+#define GD_RSPST_DISCARDED 3
+#define GD_RSPST_FALLBACK  4
+#define GD_RSP_NO_INFO 0xFFFFFFFFu
+int gd_respond_configure(gd_handle* h, const uint8_t* info_utf8, const uint32_t* info_off, uint32_t n_info);
+/* Device pointers, enqueue only. */
+int gd_respond_kinds_device(gd_handle* h, const uint8_t* d_turn, const uint8_t* d_recv_status, uint32_t n,
+                            uint8_t* d_kind, uint8_t* d_rejection_type);
+int gd_silo_index_device(gd_handle* h, const uint8_t* d_wire24, uint32_t n, uint32_t* d_silo);
+int gd_respond_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                             uint32_t n, const uint8_t* d_kind, const uint8_t* d_result,
+                             const uint8_t* d_rejection_type, const uint32_t* d_info, const uint8_t* d_body,
+                             const uint64_t* d_body_off, const uint32_t* d_order, uint8_t* d_out_buf, uint64_t out_cap,
+                             uint64_t* d_out_off, uint8_t* d_rsp_status);
+/* Host pointers, synchronous; *out_total (may be NULL) = out_off[n]. */
+int gd_respond_kinds(gd_handle* h, const uint8_t* turn, const uint8_t* recv_status, uint32_t n, uint8_t* kind,
+                     uint8_t* rejection_type);
+int gd_silo_index(gd_handle* h, const uint8_t* wire24, uint32_t n, uint32_t* silo);
+int gd_respond_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                      const uint8_t* kind, const uint8_t* result, const uint8_t* rejection_type, const uint32_t* info,
+                      const uint8_t* body, const uint64_t* body_off, const uint32_t* order, uint8_t* out_buf,
+                      uint64_t out_cap, uint64_t* out_off, uint8_t* rsp_status, uint64_t* out_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -500,7 +500,7 @@ int report_device_error(gd_handle* h) {
     GD_TRY(sync(h));
     if (e == ERR_CTX_RANGE)
         return set_err(h, GD_EINVAL, "an ActivationDirectory entry's context index is not below n_ctx");
-    if (e == 128u)   // ERR_ENC_FULL (gd_encode.h)
+    if (e == 128u)   // ERR_ENC_FULL (gd_frameout.h)
         return set_err(h, GD_EFULL, "gd_encode_frames: the encoded frames need more than out_cap bytes (out_off[n])");
     if (e & 2u) return set_err(h, GD_EFULL, "the directory table is full (device error bits 0x%x)", e);
     if (e & 4u)

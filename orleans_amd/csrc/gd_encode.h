@@ -12,6 +12,7 @@
 //                 its output length and its status
 //   k_enc_lens    lens[j] = out_len[order[j]] (+ the scan's closing 0); scan_device turns it into offsets
 //   k_enc_finish  out_off[j] as u64; the capacity check against the scanned total (ERR_ENC_FULL)
+//                 (both in gd_frameout.h, shared with the response writer)
 //   k_enc_write   the hot path.  The OUTPUT is cut into 16-KiB tiles of 16-B chunks at absolute 16-B addresses,
 //                 one workgroup a tile, one chunk a lane and step, whatever the frame lengths: a 300-KB body
 //                 and a run of 60-B frames load the lanes alike, zero-length frames cost nothing, and a chunk
@@ -32,6 +33,7 @@
 #include <cstdint>
 
 #include "gd_frames.h"
+#include "gd_frameout.h"
 #include "gd_hash.h"
 
 namespace gd {
@@ -39,7 +41,6 @@ namespace gd {
 // GD_ENC_* (include/graindispatch.h)
 enum : uint32_t { ENC_OK = 0, ENC_COPIED = 1, ENC_SKIPPED = 2, ENC_FALLBACK = 3, ENC_MALFORMED = 4, ENC_NO_ID = 5,
                   ENC_NO_SILO = 6 };
-constexpr uint32_t ERR_ENC_FULL = 128u;      // DevCounters::err: the encoded total exceeds out_cap
 constexpr uint32_t H_TRANSACTION_INFO = 1u << 27;
 constexpr uint32_t ENC_TA_LEN = 28, ENC_TS_LEN = 24;
 constexpr uint32_t ENC_MAX_TYPE = 0xFFF0u;   // longest class-name string (the plan keeps 4 + length in 16 bits)
@@ -268,33 +269,7 @@ static __global__ __launch_bounds__(BLOCK) void k_enc_plan(const uint8_t* __rest
     enc_status[i] = (uint8_t)st;
 }
 
-// lens[j] = out_len[order[j]] for j < n, lens[n] = 0 (the exclusive scan leaves the total there).  An order entry
-// that is no index of the batch is clamped: `order` is required to be a permutation.
-static __global__ __launch_bounds__(BLOCK) void k_enc_lens(const uint32_t* __restrict__ out_len,
-                                                    const uint32_t* __restrict__ order, uint32_t n,
-                                                    uint32_t* __restrict__ lens) {
-    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j > n) return;
-    lens[j] = j < n ? out_len[order ? min(order[j], n - 1) : j] : 0u;
-}
-
-static __global__ __launch_bounds__(BLOCK) void k_enc_finish(const uint32_t* __restrict__ offs, uint32_t n,
-                                                      uint64_t out_cap, unsigned long long* __restrict__ out_off,
-                                                      uint32_t* __restrict__ err) {
-    const uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
-    if (j > n) return;
-    out_off[j] = offs[j];
-    if (j == n && (uint64_t)offs[n] > out_cap) atomicOr(err, ERR_ENC_FULL);
-}
-
 // ------------------------------------------------------------------ k_enc_write
-constexpr uint32_t ENC_TILE_CHUNKS = 1024;              // 16-B chunks a workgroup: a 16-KiB tile of the output
-constexpr uint32_t ENC_TILE_FRAMES = 1024;              // frame offsets kept in LDS (4 KiB + 4); more: global search
-
-struct __attribute__((packed, aligned(4))) EncU4 {
-    uint32_t x, y, z, w;
-};
-
 struct EncArgs {
     const uint8_t* buf;
     const uint64_t* frame_off;
@@ -373,16 +348,6 @@ __device__ __forceinline__ uint32_t enc_new_bytes(const EncMap& m, uint32_t x0, 
 __device__ __forceinline__ int32_t enc_shift(const EncMap& m, uint32_t x) {
     if (m.raw) return 0;
     return x >= m.o_ts ? m.d4 : x >= m.o_ta ? m.d3 : x >= m.o_ngt ? m.d2 : x >= m.o_inp ? m.d1 : 0;
-}
-
-// The last j in [lo, hi] with so[j - base] <= pos (so is non-decreasing and so[lo - base] <= pos).
-__device__ __forceinline__ uint32_t enc_find(const uint32_t* so, uint32_t base, uint32_t lo, uint32_t hi, uint32_t pos) {
-    while (lo < hi) {
-        const uint32_t mid = lo + (hi - lo + 1) / 2;
-        if (so[mid - base] <= pos) lo = mid;
-        else hi = mid - 1;
-    }
-    return lo;
 }
 
 static __global__ __launch_bounds__(BLOCK) void k_enc_write(EncArgs a, EncTab t, uint8_t* __restrict__ out) {

@@ -180,6 +180,13 @@ struct gd_handle {
     uint32_t enc_nsilos = 0, enc_ntypes = 0, enc_maxtype = 0;   // enc_nsilos 0: not configured
     DevBuf enc_scr[3];                // plan records, output lengths, scanned offsets
 
+    // response writer (gd_respond.h, eng_respond.hip): the RejectionInfo strings and their offsets
+    // (gd_respond_configure); the silo table is the encoder's
+    DevBuf rsp_tab[2];
+    uint32_t rsp_ninfo = 0, rsp_maxinfo = 0;
+    bool rsp_configured = false;
+    DevBuf rsp_scr[3];                // plan records, output lengths, scanned offsets
+
     // activation collector (gd_collect.h, eng_collect.hip): quantum and nextTicket in ticks (gd_collect_configure)
     int64_t col_quantum = 0, col_next = 0;   // col_quantum 0: not configured
     DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller

@@ -45,6 +45,9 @@ RESP_TARGET_NOT_ME, RESP_HAS_CACHE_HEADER = 1, 2
 CB_NO_SILO = 0xFFFFFFFF
 ENC_OK, ENC_COPIED, ENC_SKIPPED, ENC_FALLBACK, ENC_MALFORMED, ENC_NO_ID, ENC_NO_SILO = range(7)
 ENC_NO_TYPE = 0xFFFFFFFF
+RSP_NONE, RSP_RESPONSE, RSP_REJECTION = range(3)
+RSPST_OK, RSPST_SKIPPED, RSPST_MALFORMED, RSPST_DISCARDED, RSPST_FALLBACK = range(5)
+RSP_NO_INFO = 0xFFFFFFFF
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -107,6 +110,8 @@ EXPORTED_SYMBOLS = [
     "gd_classes_set", "gd_classes_get", "gd_route_compact", "gd_route_bucket_compact", "gd_route_compact_device",
     "gd_route_bucket_compact_device",
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
+    "gd_respond_configure", "gd_respond_kinds_device", "gd_respond_kinds", "gd_silo_index_device", "gd_silo_index",
+    "gd_respond_frames_device", "gd_respond_frames",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
@@ -454,6 +459,13 @@ def _load() -> C.CDLL:
         "gd_encode_configure": (C.c_int, [P, P, U32, P, P, U32]),
         "gd_encode_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_encode_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
+        "gd_respond_configure": (C.c_int, [P, P, P, U32]),
+        "gd_respond_kinds_device": (C.c_int, [P, P, P, U32, P, P]),
+        "gd_respond_kinds": (C.c_int, [P, P, P, U32, P, P]),
+        "gd_silo_index_device": (C.c_int, [P, P, U32, P]),
+        "gd_silo_index": (C.c_int, [P, P, U32, P]),
+        "gd_respond_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, P, U64, P, P]),
+        "gd_respond_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
         "gd_collect_configure": (C.c_int, [P, I64, I64]),
         "gd_collect_next_ticket": (C.c_int, [P, C.POINTER(I64)]),
         "gd_collect_schedule_device": (C.c_int, [P, CS, U32, P, U32, I64, P]),
@@ -2467,6 +2479,74 @@ class GrainDispatch:
                                             C.c_void_p(d_placed or 0), C.c_void_p(d_new_type or 0),
                                             C.c_void_p(d_order or 0), C.c_void_p(d_out), out_cap,
                                             C.c_void_p(d_out_off), C.c_void_p(d_enc_status)))
+
+    # -- response writer (CreateResponseMessage / CreateRejectionResponse + Message.Serialize) ------
+    def respond_configure(self, infos: Sequence[str] = ()):
+        """gd_respond_configure: infos[k] = the RejectionInfo string info index k stands for."""
+        blobs = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in infos]
+        off = np.zeros(len(blobs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+        utf8 = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
+        self._c(lib.gd_respond_configure(self.h, _ptr(utf8), _ptr(off), len(blobs)))
+
+    def respond_kinds(self, turn, recv_status=None):
+        """gd_respond_kinds: (kind u8[n], rejection_type u8[n])."""
+        t = np.ascontiguousarray(np.asarray(turn, dtype=np.uint8))
+        r = self._opt(recv_status, np.uint8)
+        n = len(t)
+        kind, rej = np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self._c(lib.gd_respond_kinds(self.h, _ptr(t), None if r is None else _ptr(r), n, _ptr(kind), _ptr(rej)))
+        return kind, rej
+
+    def respond_kinds_device(self, d_turn: int, d_recv_status: Optional[int], n: int, d_kind: int,
+                             d_rejection_type: int):
+        self._c(lib.gd_respond_kinds_device(self.h, C.c_void_p(d_turn), C.c_void_p(d_recv_status or 0), n,
+                                            C.c_void_p(d_kind), C.c_void_p(d_rejection_type)))
+
+    def silo_index(self, wire24):
+        """gd_silo_index: wire24 = (n, 24) u8 wire SiloAddresses -> silo index u32[n] (NO_SILO: not in the table)."""
+        w = np.ascontiguousarray(np.asarray(wire24, dtype=np.uint8).reshape(-1, 24))
+        n = len(w)
+        silo = np.zeros(n, np.uint32)
+        self._c(lib.gd_silo_index(self.h, _ptr(w) if n else None, n, _ptr(silo) if n else None))
+        return silo
+
+    def silo_index_device(self, d_wire24: int, n: int, d_silo: int):
+        self._c(lib.gd_silo_index_device(self.h, C.c_void_p(d_wire24), n, C.c_void_p(d_silo)))
+
+    def respond_frames(self, buf: bytes, offsets, kind, result=None, rejection_type=None, info=None, body=None,
+                       body_off=None, order=None, out_cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """gd_respond_frames: (out bytes u8[out_cap], out_off u64[n + 1], rsp_status u8[n], total).  `out`: a
+        caller's u8 array to write into (its length is out_cap)."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        k = np.ascontiguousarray(np.asarray(kind, dtype=np.uint8))
+        rs, rt, inf = self._opt(result, np.uint8), self._opt(rejection_type, np.uint8), self._opt(info, np.uint32)
+        bo, od = self._opt(body_off, np.uint64), self._opt(order, np.uint32)
+        bd = None
+        if body is not None and bo is not None:
+            bd = np.frombuffer(bytes(body), dtype=np.uint8) if len(body) else np.zeros(1, dtype=np.uint8)
+        nbody = int(bo[-1]) if bd is not None and len(bo) else 0
+        if out is None:
+            out = np.zeros(len(buf) + nbody + n * (16 + 256) if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        st = np.zeros(n, np.uint8)
+        total = C.c_uint64(0)
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_respond_frames(self.h, _ptr(b), len(buf), _ptr(off), n, _ptr(k), p(rs), p(rt), p(inf), p(bd),
+                                      p(bo) if bd is not None else None, p(od), _ptr(out) if len(out) else None,
+                                      len(out), _ptr(out_off), _ptr(st), C.byref(total)))
+        return out, out_off, st, int(total.value)
+
+    def respond_frames_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, d_kind: int,
+                              d_result: Optional[int], d_rejection_type: Optional[int], d_info: Optional[int],
+                              d_body: Optional[int], d_body_off: Optional[int], d_order: Optional[int], d_out: int,
+                              out_cap: int, d_out_off: int, d_rsp_status: int):
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_respond_frames_device(self.h, v(d_buf), buf_len, v(d_offsets), n, v(d_kind), v(d_result),
+                                             v(d_rejection_type), v(d_info), v(d_body), v(d_body_off), v(d_order),
+                                             v(d_out), out_cap, v(d_out_off), v(d_rsp_status)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
