@@ -2257,6 +2257,120 @@ int gd_respond_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const 
                       const uint8_t* body, const uint64_t* body_off, const uint32_t* order, uint8_t* out_buf,
                       uint64_t out_cap, uint64_t* out_off, uint8_t* rsp_status, uint64_t* out_total);
 
+/* ---- request writer: CreateMessage + SendRequest + SetTargetPlacement + Serialize for a batch ----
+ * A grain call becomes a message in MessageFactory.CreateMessage (MessageFactory.cs:21-47, from InsideRuntimeClient.
+ * SendRequest, InsideRuntimeClient.cs:120-229); SendRequestMessage fills in the sender, the target, DebugContext,
+ * GenericGrainType and TimeToLive; Dispatcher.SendMessage addresses it (gd_route), calls SetTargetPlacement
+ * (Message.cs:629-639) and the message is serialized (Message.cs:481-516).  Here the frame
+ * [int32 headerLength][int32 bodyLength][header][body] is written from a few words per message: no C# Message,
+ * no HeadersContainer, no source frame.  For message i the header is what HeadersContainer.Serializer
+ * (Message.cs:1126-1245) writes under the mask GetHeadersMask (:1075-1117) gives, in this order:
+ *   Category          always, byte 2 (Categories.Application)
+ *   DebugContext      when debug[i] indexes a non-empty string of gd_request_configure: int32 UTF-8 length + bytes
+ *   Direction         always: byte 0 (Request), byte 2 (OneWay) with GD_REQ_ONE_WAY
+ *   TimeToLive        ttl_ticks, 8 bytes as given (the reference writes ResponseTimeout minus the time since
+ *                     creation: the value is the caller's), unless ttl_ticks == GD_TTL_NONE, the message is OneWay,
+ *                     or GD_REQ_NO_TTL is set (system grains: Message.IsExpirableMessage, Message.cs:304-313)
+ *   GenericGrainType  when generic[i] indexes a non-empty string of the same table
+ *   CorrelationId     always, id_base + i, 8 bytes (CorrelationId.GetNext for a batch: the caller reserves n ids)
+ *   AlwaysInterleave, IsNewPlacement, ReadOnly, IsUnordered   the mask bit and a True token (byte 3) each:
+ *                     GD_REQ_ALWAYS_INTERLEAVE / _READ_ONLY / _UNORDERED; IsNewPlacement when addressed and
+ *                     placed[i] == GD_PLACED_NEW (the encoder's rule); absent otherwise
+ *   NewGrainType      when addressed and new_type[i] indexes a non-empty string of gd_encode_configure's type table
+ *   SendingActivation the ActivationId of sender_act[i] (gd_activation_ids_set) as a UniqueKey, null KeyExt: 28 B
+ *   SendingGrain      sender_grain[i], its KeyExt from sender_ext when given (else null)
+ *   SendingSilo       gd_encode_configure's silos[gd_config.my_silo]: 24 B
+ *   TargetActivation  when addressed: the ActivationId of act[i], as gd_encode_frames writes it
+ *   TargetGrain       target[i], its KeyExt from target_ext when given
+ *   TargetSilo        when addressed: silos[silo[i]], as gd_encode_frames writes it
+ *   mask-only bits    26 (IsUsingInterfaceVersion) with GD_REQ_IFACE_VERSION, 28 (IsTransactionRequired) with
+ *                     GD_REQ_TXN_REQUIRED
+ *   never written     ForwardCount, ResendCount, Result, RejectionType / Info, CacheInvalidationHeader,
+ *                     RequestContext, TargetObserver, TransactionInfo
+ * "Addressed": the route arrays (d_silo, d_act, d_status: together or not at all) are given and
+ * status[i] == GD_ROUTE_OK.  The body is body[body_off[i] .. body_off[i + 1]), copied as given (gd_respond_frames'
+ * conventions: n + 1 non-decreasing entries, body and body_off a pair, the library invents no body bytes).
+ * A KeyExt is gd_key_ext's: length[i] = GD_KEYEXT_NULL, or the UTF-8 bytes at offset[i]; the struct is a host
+ * struct, its arrays device pointers in the device forms.
+ * Status, one byte per message, decided in this order:
+ *   a target_ext / sender_ext length of GD_KEYEXT_HOST (or any other length below -1, or a string that runs
+ *     past bytes_len)                                                -> GD_REQ_FALLBACK
+ *   TargetGrain a system target (UniqueKey category 1: ActivationId.GetSystemActivation and the Ping / System
+ *     categories, InsideRuntimeClient.cs:182-189)                     -> GD_REQ_FALLBACK
+ *   sender_act[i] has no ActivationId (past the map, or all zero)     -> GD_REQ_NO_ID
+ *   addressed and silo[i] >= n_silos                                  -> GD_REQ_NO_SILO
+ *   addressed and act[i] has no ActivationId                          -> GD_REQ_NO_ID
+ *   addressed                                                         -> GD_REQ_OK
+ *   else (a miss, any other route status, no route arrays)            -> GD_REQ_UNADDRESSED: the frame is written
+ *     without TargetActivation, TargetSilo, IsNewPlacement and NewGrainType; C# takes it to AddressMessageAsync
+ * Only OK and UNADDRESSED frames contribute bytes.  order, out_off[n + 1], out_cap and GD_EFULL (nothing written,
+ * out_off still complete, the handle's device error word) and n == 0 are gd_encode_frames*'s.  Totals are 32-bit:
+ * a call whose bound n * (206 + 2 * longest request string + longest type string) + KeyExt bytes + body bytes
+ * reaches 2^32 is refused with GD_EINVAL; the device forms cannot see the KeyExt lengths and body_off, check the
+ * rest and leave those bytes to the caller.  GD_ESTATE before gd_encode_configure or gd_request_configure, when
+ * gd_config.my_silo is not in gd_encode_configure's table, and inside a hipGraph capture.
+ * target_ext, sender_ext, options, generic, debug, body / body_off may be NULL: no KeyExt, options 0, no strings,
+ * empty bodies.  Every route array and d_order may be NULL.
+ * gd_request_configure installs the one string table debug[i] and generic[i] index (a string holds at most 65520
+ * bytes; str_off[0] = 0, n_str + 1 non-decreasing entries; an index >= n_str names none).  It may be repeated
+ * (n_str may be 0) and synchronises the handle first.
+ * gd_request_send*: the head of the send path in one call, no host round trip in the device form: gd_route on
+ * `target`, gd_send_queues with category Application and per message the TimeToLive its frame carries (ttl_ticks,
+ * or none), then the writer with order = the send stage's perm, so each sender queue's requests are one contiguous
+ * byte run: queue q owns [out_off[offsets[q]], out_off[offsets[q + 1]]).  It returns the outputs of all three
+ * stages (d_queue may be NULL); GD_ESTATE before gd_send_configure too.  Frames of messages the send stage does
+ * not queue (held, expired) are still written, in the trailing bucket.
+ * Left to C#: observer references (TargetObserver), calls under a non-empty ambient RequestContext or an ambient
+ * transaction (TransactionInfo.Fork), system-target senders and targets, body serialization, and the callback
+ * object.  Registering the callbacks needs no device result: the ids are id_base + i and the caller knows which
+ * calls are one-way, so it calls gd_callbacks_add* with its own arrays. */
+#define GD_REQ_ONE_WAY           1u
+#define GD_REQ_NO_TTL            2u
+#define GD_REQ_ALWAYS_INTERLEAVE 4u
+#define GD_REQ_READ_ONLY         8u
+#define GD_REQ_UNORDERED         16u
+#define GD_REQ_IFACE_VERSION     32u
+#define GD_REQ_TXN_REQUIRED      64u
+#define GD_REQ_OK          0
+#define GD_REQ_UNADDRESSED 1
+#define GD_REQ_FALLBACK    2
+#define GD_REQ_NO_ID       3
+#define GD_REQ_NO_SILO     4
+#define GD_REQ_NO_STRING 0xFFFFFFFFu
+typedef struct gd_request_batch {
+    const gd_key*     target;        /* [n] TargetGrain                                         */
+    const gd_key_ext* target_ext;    /* its KeyExt strings; NULL: every KeyExt null             */
+    const gd_key*     sender_grain;  /* [n] SendingGrain                                        */
+    const gd_key_ext* sender_ext;    /* NULL: every KeyExt null                                 */
+    const uint32_t*   sender_act;    /* [n] the sender's activation index                       */
+    const uint8_t*    options;       /* [n] GD_REQ_* bits; NULL: 0                              */
+    const uint32_t*   generic;       /* [n] GenericGrainType string index; NULL: none           */
+    const uint32_t*   debug;         /* [n] DebugContext string index; NULL: none               */
+    int64_t           id_base;       /* CorrelationId of message 0                              */
+    int64_t           ttl_ticks;     /* TimeToLive in TimeSpan ticks; GD_TTL_NONE: none         */
+    const uint8_t*    body;          /* the bodies, concatenated; NULL (or body_off NULL): empty */
+    const uint64_t*   body_off;      /* [n + 1]                                                 */
+} gd_request_batch;
+int gd_request_configure(gd_handle* h, const uint8_t* str_utf8, const uint32_t* str_off, uint32_t n_str);
+/* Device pointers (the batch struct and the gd_key_ext structs are host structs), enqueue only, no host read-back. */
+int gd_request_frames_device(gd_handle* h, const gd_request_batch* batch, uint32_t n, const uint32_t* d_silo,
+                             const uint32_t* d_act, const uint8_t* d_status, const uint8_t* d_placed,
+                             const uint32_t* d_new_type, const uint32_t* d_order, uint8_t* d_out_buf, uint64_t out_cap,
+                             uint64_t* d_out_off, uint8_t* d_req_status);
+int gd_request_send_device(gd_handle* h, const gd_request_batch* batch, uint32_t n, uint32_t* d_silo, uint32_t* d_act,
+                           uint8_t* d_status, uint8_t* d_send_status, uint32_t* d_queue, uint32_t* d_perm,
+                           uint32_t* d_offsets, uint8_t* d_out_buf, uint64_t out_cap, uint64_t* d_out_off,
+                           uint8_t* d_req_status);
+/* Host pointers, synchronous; *out_total (may be NULL) = out_off[n]. */
+int gd_request_frames(gd_handle* h, const gd_request_batch* batch, uint32_t n, const uint32_t* silo,
+                      const uint32_t* act, const uint8_t* status, const uint8_t* placed, const uint32_t* new_type,
+                      const uint32_t* order, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off,
+                      uint8_t* req_status, uint64_t* out_total);
+int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uint32_t* out_silo, uint32_t* out_act,
+                    uint8_t* out_status, uint8_t* out_send_status, uint32_t* out_queue, uint32_t* out_perm,
+                    uint32_t* out_offsets, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off, uint8_t* req_status,
+                    uint64_t* out_total);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,13 @@ struct gd_handle {
     bool rsp_configured = false;
     DevBuf rsp_scr[3];                // plan records, output lengths, scanned offsets
 
+    // request writer (gd_request.h, eng_request.hip): the DebugContext / GenericGrainType strings and their
+    // offsets (gd_request_configure); the ActivationIds, silos and type names are the encoder's
+    DevBuf req_tab[2];
+    uint32_t req_nstr = 0, req_maxstr = 0;
+    bool req_configured = false;
+    DevBuf req_scr[4];                // plan records, output lengths, scanned offsets, the send stage's ttl
+
     // activation collector (gd_collect.h, eng_collect.hip): quantum and nextTicket in ticks (gd_collect_configure)
     int64_t col_quantum = 0, col_next = 0;   // col_quantum 0: not configured
     DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller

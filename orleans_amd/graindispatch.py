@@ -48,6 +48,10 @@ ENC_NO_TYPE = 0xFFFFFFFF
 RSP_NONE, RSP_RESPONSE, RSP_REJECTION = range(3)
 RSPST_OK, RSPST_SKIPPED, RSPST_MALFORMED, RSPST_DISCARDED, RSPST_FALLBACK = range(5)
 RSP_NO_INFO = 0xFFFFFFFF
+(REQ_ONE_WAY, REQ_NO_TTL, REQ_ALWAYS_INTERLEAVE, REQ_READ_ONLY, REQ_UNORDERED, REQ_IFACE_VERSION,
+ REQ_TXN_REQUIRED) = (1 << k for k in range(7))
+REQ_OK, REQ_UNADDRESSED, REQ_FALLBACK, REQ_NO_ID, REQ_NO_SILO = range(5)
+REQ_NO_STRING = 0xFFFFFFFF
 CFG_KERNEL_TIMING = 1
 CFG_NO_LANE_ORDER = 2
 
@@ -112,6 +116,8 @@ EXPORTED_SYMBOLS = [
     "gd_encode_configure", "gd_encode_frames_device", "gd_encode_frames",
     "gd_respond_configure", "gd_respond_kinds_device", "gd_respond_kinds", "gd_silo_index_device", "gd_silo_index",
     "gd_respond_frames_device", "gd_respond_frames",
+    "gd_request_configure", "gd_request_frames_device", "gd_request_frames", "gd_request_send_device",
+    "gd_request_send",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
@@ -283,6 +289,13 @@ class KeyExtBatch:
                 pos += len(b)
         self.blob = np.frombuffer(b"".join(parts) + b"\0", dtype=np.uint8).copy()
         self.struct = gd_key_ext(self.blob.ctypes.data, self.offset.ctypes.data, self.length.ctypes.data, pos)
+
+
+class gd_request_batch(C.Structure):
+    _fields_ = [("target", C.c_void_p), ("target_ext", C.POINTER(gd_key_ext)), ("sender_grain", C.c_void_p),
+                ("sender_ext", C.POINTER(gd_key_ext)), ("sender_act", C.c_void_p), ("options", C.c_void_p),
+                ("generic", C.c_void_p), ("debug", C.c_void_p), ("id_base", C.c_int64), ("ttl_ticks", C.c_int64),
+                ("body", C.c_void_p), ("body_off", C.c_void_p)]
 
 
 GD_MULTI_RETURN_ROUTES = 1
@@ -466,6 +479,13 @@ def _load() -> C.CDLL:
         "gd_silo_index": (C.c_int, [P, P, U32, P]),
         "gd_respond_frames_device": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, P, U64, P, P]),
         "gd_respond_frames": (C.c_int, [P, P, U64, P, U32, P, P, P, P, P, P, P, P, U64, P, P, C.POINTER(U64)]),
+        "gd_request_configure": (C.c_int, [P, P, P, U32]),
+        "gd_request_frames_device": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, U64, P, P]),
+        "gd_request_frames": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, U64, P, P,
+                                        C.POINTER(U64)]),
+        "gd_request_send_device": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, P, U64, P, P]),
+        "gd_request_send": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, P, U64, P, P,
+                                      C.POINTER(U64)]),
         "gd_collect_configure": (C.c_int, [P, I64, I64]),
         "gd_collect_next_ticket": (C.c_int, [P, C.POINTER(I64)]),
         "gd_collect_schedule_device": (C.c_int, [P, CS, U32, P, U32, I64, P]),
@@ -2547,6 +2567,101 @@ class GrainDispatch:
         self._c(lib.gd_respond_frames_device(self.h, v(d_buf), buf_len, v(d_offsets), n, v(d_kind), v(d_result),
                                              v(d_rejection_type), v(d_info), v(d_body), v(d_body_off), v(d_order),
                                              v(d_out), out_cap, v(d_out_off), v(d_rsp_status)))
+
+    # -- request writer (CreateMessage + SendRequest + SetTargetPlacement + Message.Serialize) -------
+    def request_configure(self, strings: Sequence[str] = ()):
+        """gd_request_configure: strings[k] = the DebugContext / GenericGrainType string index k stands for."""
+        blobs = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in strings]
+        off = np.zeros(len(blobs) + 1, np.uint32)
+        off[1:] = np.cumsum([len(b) for b in blobs], dtype=np.uint64)
+        utf8 = np.frombuffer(b"".join(blobs) or b"\0", dtype=np.uint8)
+        self._c(lib.gd_request_configure(self.h, _ptr(utf8), _ptr(off), len(blobs)))
+
+    def _request_batch(self, target, sender_grain, sender_act, target_ext=None, sender_ext=None, options=None,
+                       generic=None, debug=None, id_base: int = 0, ttl_ticks: int = TTL_NONE, body=None,
+                       body_off=None):
+        """(gd_request_batch with host pointers, n, body bytes, the arrays it points at).  target_ext / sender_ext:
+        a KeyExtBatch or a list of its items."""
+        tg, sg = keys_array(target), keys_array(sender_grain)
+        n = len(tg)
+        sa = np.ascontiguousarray(np.asarray(sender_act, dtype=np.uint32))
+        tx = target_ext if target_ext is None or isinstance(target_ext, KeyExtBatch) else KeyExtBatch(target_ext)
+        sx = sender_ext if sender_ext is None or isinstance(sender_ext, KeyExtBatch) else KeyExtBatch(sender_ext)
+        op, ge, db = self._opt(options, np.uint8), self._opt(generic, np.uint32), self._opt(debug, np.uint32)
+        bo = self._opt(body_off, np.uint64)
+        bd = None
+        if body is not None and bo is not None:
+            bd = np.frombuffer(bytes(body), dtype=np.uint8) if len(body) else np.zeros(1, dtype=np.uint8)
+        p = lambda a: None if a is None else _ptr(a)
+        b = gd_request_batch(_ptr(tg), None if tx is None else C.pointer(tx.struct), _ptr(sg),
+                             None if sx is None else C.pointer(sx.struct), _ptr(sa), p(op), p(ge), p(db), id_base,
+                             ttl_ticks, p(bd), p(bo) if bd is not None else None)
+        nbody = int(bo[-1]) if bd is not None and len(bo) else 0
+        return b, n, nbody + sum(int(x.blob.size) for x in (tx, sx) if x is not None), (tg, sg, sa, tx, sx, op, ge, db, bd, bo)
+
+    def request_frames(self, batch: dict, silo=None, act=None, status=None, placed=None, new_type=None, order=None,
+                       out_cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """gd_request_frames: (out bytes u8[out_cap], out_off u64[n + 1], req_status u8[n], total).  batch: the
+        keyword arguments of _request_batch."""
+        b, n, extra, keep = self._request_batch(**batch)
+        sl, ac, st = self._opt(silo, np.uint32), self._opt(act, np.uint32), self._opt(status, np.uint8)
+        pl, nt, od = self._opt(placed, np.uint8), self._opt(new_type, np.uint32), self._opt(order, np.uint32)
+        if out is None:
+            out = np.zeros(extra + n * 512 if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        rst = np.zeros(n, np.uint8)
+        total = C.c_uint64(0)
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_request_frames(self.h, C.byref(b), n, p(sl), p(ac), p(st), p(pl), p(nt), p(od),
+                                      _ptr(out) if len(out) else None, len(out), _ptr(out_off), _ptr(rst),
+                                      C.byref(total)))
+        return out, out_off, rst, int(total.value)
+
+    @staticmethod
+    def _request_batch_device(d: dict):
+        """gd_request_batch from device addresses; target_ext / sender_ext: (d_bytes, d_offset, d_length, bytes_len)."""
+        v = lambda k: d.get(k) or None
+        exts = [None if d.get(k) is None else gd_key_ext(*d[k]) for k in ("target_ext", "sender_ext")]
+        b = gd_request_batch(v("target"), None if exts[0] is None else C.pointer(exts[0]), v("sender_grain"),
+                             None if exts[1] is None else C.pointer(exts[1]), v("sender_act"), v("options"),
+                             v("generic"), v("debug"), d.get("id_base", 0), d.get("ttl_ticks", TTL_NONE), v("body"),
+                             v("body_off"))
+        return b, exts
+
+    def request_frames_device(self, d_batch: dict, n: int, d_silo: Optional[int], d_act: Optional[int],
+                              d_status: Optional[int], d_placed: Optional[int], d_new_type: Optional[int],
+                              d_order: Optional[int], d_out: int, out_cap: int, d_out_off: int, d_req_status: int):
+        b, keep = self._request_batch_device(d_batch)
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_request_frames_device(self.h, C.byref(b), n, v(d_silo), v(d_act), v(d_status), v(d_placed),
+                                             v(d_new_type), v(d_order), v(d_out), out_cap, v(d_out_off),
+                                             v(d_req_status)))
+
+    def request_send(self, batch: dict, out_cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> dict:
+        """gd_request_send: route + sender queues + writer; a dict of every stage's outputs."""
+        b, n, extra, keep = self._request_batch(**batch)
+        silo, act, perm = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        status, sst, rst = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        q = np.zeros(n, np.uint32)
+        offsets = np.zeros(getattr(self, "send_n_queues", 0) + 5, np.uint32)   # GD_ESTATE before send_configure
+        if out is None:
+            out = np.zeros(extra + n * 512 if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        total = C.c_uint64(0)
+        self._c(lib.gd_request_send(self.h, C.byref(b), n, _ptr(silo), _ptr(act), _ptr(status), _ptr(sst), _ptr(q),
+                                    _ptr(perm), _ptr(offsets), _ptr(out) if len(out) else None, len(out),
+                                    _ptr(out_off), _ptr(rst), C.byref(total)))
+        return {"silo": silo, "act": act, "status": status, "send_status": sst, "queue": q, "perm": perm,
+                "offsets": offsets, "out": out, "out_off": out_off, "req_status": rst, "total": int(total.value)}
+
+    def request_send_device(self, d_batch: dict, n: int, d_silo: int, d_act: int, d_status: int, d_send_status: int,
+                            d_queue: Optional[int], d_perm: int, d_offsets: int, d_out: int, out_cap: int,
+                            d_out_off: int, d_req_status: int):
+        b, keep = self._request_batch_device(d_batch)
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_request_send_device(self.h, C.byref(b), n, v(d_silo), v(d_act), v(d_status), v(d_send_status),
+                                           v(d_queue), v(d_perm), v(d_offsets), v(d_out), out_cap, v(d_out_off),
+                                           v(d_req_status)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
