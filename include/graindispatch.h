@@ -2371,6 +2371,127 @@ int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uin
                     uint32_t* out_offsets, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off, uint8_t* req_status,
                     uint64_t* out_total);
 
+/* ---- forward writer: TryForwardRequest + AddressMessage + Serialize for a batch --------------------
+ * A request that reached an invalid or stuck activation (gd_turns*: GD_TURN_FORWARD, GD_TURN_STUCK), or that stood
+ * on the waiting list of a deactivated one (Dispatcher.ProcessRequestsToInvalidActivation, Dispatcher.cs:486-524),
+ * is forwarded: Dispatcher.TryForwardRequest (:526-570) appends the old address to the CacheInvalidationHeader,
+ * TryForwardMessage (:591-599) tests MayForward and counts ForwardCount up, ResendMessageImpl (:601-623) sets the
+ * forwarding address or clears the target address and sends the message through AddressMessage again, and the
+ * message is serialized (Message.cs:481-516).  Here the source frames are read where the receive stages left them
+ * (buf, buf_len, frame_off[n], as gd_respond_frames) and the forwarded frames are written as frames, output frame
+ * j being input frame order[j].
+ *   kind[i]: GD_FWD_FORWARD, or GD_FWD_NONE (any other byte) for a message that does not leave here -- also the
+ *     cross-cluster return of TryForwardRequest (:539-546), which stays in C#.
+ *   old_act[i]: the invalid activation's index (its ActivationId: gd_activation_ids_set); GD_NO_ACTIVATION:
+ *     oldAddress == null.  old_act NULL: none has one.
+ *   fwd_silo[i], fwd_act[i]: the forwarding address; fwd_silo[i] == GD_NO_SILO: none.  The pair may be NULL.
+ *   silo[i], act[i], status[i], placed[i], new_type[i]: the route's results for the frames that leave without a
+ *     forwarding address, with gd_encode_frames' meaning; the three route arrays go together and, like placed and
+ *     new_type, may be NULL.
+ *   max_forward_count: SiloMessagingOptions.MaxForwardCount (default 2).  local_silo: this silo's index in
+ *     gd_encode_configure's table (oldAddress is always an address on this silo).
+ * The CacheInvalidationHeader is a sized field: HeadersContainer.Serializer writes an int32 count and then every
+ * entry through the registered ActivationAddress serializer, which writes, with no type token, the SiloAddress
+ * (24 B), the GrainId UniqueKey (24 B + KeyExt string) and the ActivationId UniqueKey (24 B + KeyExt string)
+ * (Message.cs:1132-1140, :1363-1367; BuiltInTypes.cs:2059-2063; BinaryTokenStreamWriter.cs:27-35): 80 B an entry
+ * for a long-keyed grain.  It stands first, right behind the mask.
+ * The output header, in HeadersContainer.Serializer order (Message.cs:1126-1244):
+ *   CacheInvalidationHeader  when old_act[i] names an activation: count = old count + 1 (1 when the field was
+ *                     absent), the old entries as they stand, then one entry: silos[local_silo] (24 B), the
+ *                     frame's own TargetGrain UniqueKey with its KeyExt bytes as they stand, the ActivationId of
+ *                     old_act[i] with a null KeyExt (28 B); the mask gains bit 1.  Else as in the source.
+ *                     (Message.AddToCacheInvalidationHeader, Message.cs:333-343; ahead of MayForward, as in C#.)
+ *   ForwardCount      old value + 1 (absent counts as 0) as an int32, behind TimeToLive and in front of
+ *                     GenericGrainType: replaced, or inserted; field and bit are dropped when the new value is 0
+ *                     (GetHeadersMask, Message.cs:1093)
+ *   forwarding address given: TargetActivation = the ActivationId of fwd_act[i] (28 B), TargetSilo =
+ *                     silos[fwd_silo[i]], replaced or inserted at gd_encode_frames' positions; IsNewPlacement is
+ *                     removed, token and bit (:612-613).  TargetGrain stays the frame's.
+ *   no forwarding address: TargetActivation and TargetSilo are removed (:618-620); then, when status[i] ==
+ *                     GD_ROUTE_OK, Message.SetTargetPlacement exactly as gd_encode_frames applies it:
+ *                     TargetActivation, TargetSilo, IsNewPlacement by placed[i], NewGrainType by new_type[i].
+ *                     Otherwise the frame leaves unaddressed, for AddressMessageAsync.
+ *   everything else   headerLength is rewritten, bodyLength is not; every other header byte, and the body, is
+ *                     copied in order (the encoder's copy rule; it also defines the result for frames the
+ *                     reference's serializer would not emit).  TargetHistory is not a wire field.
+ * Status, one byte per input frame, decided in this order:
+ *   kind not GD_FWD_FORWARD                                        -> GD_FWDST_SKIPPED
+ *   the decoder's GD_FRAME_MALFORMED length conditions; a negative invalidation count; the walk runs off the
+ *     header (the walk ends in front of RequestContext, and behind TargetGrain when TargetObserver and
+ *     TransactionInfo are both present)                             -> GD_FWDST_MALFORMED
+ *   RequestContext present; TargetObserver and TransactionInfo both present; TargetGrain absent; TargetGrain a
+ *     system target (SendSystemTargetMessage, :606-609)             -> GD_FWDST_FALLBACK, C# forwards it
+ *   ForwardCount >= max_forward_count (MayForward, :627-630)        -> GD_FWDST_REJECT: no bytes; the reference's
+ *     rejection carries the extended invalidation header (MessageFactory.cs:90), which gd_respond_frames does not
+ *     write: C# rejects it
+ *   old_act[i] names an activation and local_silo >= n_silos        -> GD_FWDST_NO_SILO
+ *   old_act[i] names an activation without an ActivationId          -> GD_FWDST_NO_ID
+ *   the address written (the forwarding address, else the route's): its silo >= n_silos -> GD_FWDST_NO_SILO,
+ *     its activation without an ActivationId                        -> GD_FWDST_NO_ID
+ *   else                                   -> GD_FWDST_OK_ADDRESSED, or GD_FWDST_OK_UNADDRESSED (no address written)
+ * Only the two OK statuses contribute bytes.  target[i] (may be NULL) = the frame's TargetGrain for every status
+ * but SKIPPED, MALFORMED and FALLBACK (zeros there): the caller routes or places the unaddressed frames without a
+ * second decode.  order, out_off[n + 1], out_cap, GD_EFULL (nothing written, out_off still complete, the handle's
+ * device error word) and n == 0 are gd_encode_frames*'s.  Totals are 32-bit: a frame gains at most the count (4),
+ * one entry (80 + its TargetGrain KeyExt bytes), ForwardCount (4) and the encoder's 57 + the longest type string,
+ * and the KeyExt bytes of all frames lie in buf, so a call whose bound
+ *   2 * buf_len + n * (145 + longest configured type string)
+ * reaches 2^32 is refused with GD_EINVAL.  Frames must be disjoint ranges of buf.  GD_ESTATE before
+ * gd_encode_configure, and inside a hipGraph capture.
+ * gd_forward_kinds*: GD_TURN_FORWARD and GD_TURN_STUCK -> GD_FWD_FORWARD, everything else GD_FWD_NONE.
+ * gd_forward_send*: the chain, no host round trip in the device form: the plan; gd_route on `target`; the merge
+ * into silo / act / status (a frame that does not leave: GD_NO_SILO, GD_NO_ACTIVATION, GD_ROUTE_UNDECODED; a
+ * forwarding address wins over the route: its silo, its activation, GD_ROUTE_OK; a TargetGrain with a KeyExt
+ * string: GD_ROUTE_KEYEXT; else the route's result); gd_send_queues with each frame's own Category (absent: 0)
+ * and TimeToLive; then the writer with order = the send stage's perm and the address of every GD_ROUTE_OK message,
+ * so each sender queue's forwarded frames are one contiguous byte run: queue q owns
+ * [out_off[offsets[q]], out_off[offsets[q + 1]]).  It returns the outputs of all three stages (d_queue may be
+ * NULL; target is required); GD_ESTATE before gd_send_configure too.  Misses leave unaddressed: gd_route_place* on
+ * the returned keys is the caller's next step.
+ * Left to C#: the rejections of messages that may not forward, the cross-cluster return, system targets,
+ * InvalidateCacheEntry on the receiving side, and FALLBACK frames. */
+#define GD_FWD_NONE    0
+#define GD_FWD_FORWARD 1
+#define GD_FWDST_OK_ADDRESSED   0
+#define GD_FWDST_OK_UNADDRESSED 1
+#define GD_FWDST_SKIPPED        2
+#define GD_FWDST_MALFORMED      3
+#define GD_FWDST_FALLBACK       4
+#define GD_FWDST_REJECT         5
+#define GD_FWDST_NO_SILO        6
+#define GD_FWDST_NO_ID          7
+typedef struct gd_forward_batch {
+    const uint8_t*  buf;                /* the receive buffer                                      */
+    uint64_t        buf_len;
+    const uint64_t* frame_off;          /* [n] first byte of every frame                           */
+    const uint8_t*  kind;               /* [n] GD_FWD_*                                            */
+    const uint32_t* old_act;            /* [n] or NULL                                             */
+    const uint32_t* fwd_silo;           /* [n] or NULL (with fwd_act)                              */
+    const uint32_t* fwd_act;            /* [n] or NULL                                             */
+    int32_t         max_forward_count;  /* SiloMessagingOptions.MaxForwardCount                    */
+    uint32_t        local_silo;         /* index into gd_encode_configure's table                  */
+} gd_forward_batch;
+/* Device pointers (the batch struct is a host struct), enqueue only, no host read-back. */
+int gd_forward_kinds_device(gd_handle* h, const uint8_t* d_turn, uint32_t n, uint8_t* d_kind);
+int gd_forward_frames_device(gd_handle* h, const gd_forward_batch* batch, uint32_t n, const uint32_t* d_silo,
+                             const uint32_t* d_act, const uint8_t* d_status, const uint8_t* d_placed,
+                             const uint32_t* d_new_type, const uint32_t* d_order, uint8_t* d_out_buf, uint64_t out_cap,
+                             uint64_t* d_out_off, uint8_t* d_fwd_status, gd_key* d_target);
+int gd_forward_send_device(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uint32_t* d_silo, uint32_t* d_act,
+                           uint8_t* d_status, uint8_t* d_send_status, uint32_t* d_queue, uint32_t* d_perm,
+                           uint32_t* d_offsets, uint8_t* d_out_buf, uint64_t out_cap, uint64_t* d_out_off,
+                           uint8_t* d_fwd_status, gd_key* d_target);
+/* Host pointers, synchronous; *out_total (may be NULL) = out_off[n]. */
+int gd_forward_kinds(gd_handle* h, const uint8_t* turn, uint32_t n, uint8_t* kind);
+int gd_forward_frames(gd_handle* h, const gd_forward_batch* batch, uint32_t n, const uint32_t* silo,
+                      const uint32_t* act, const uint8_t* status, const uint8_t* placed, const uint32_t* new_type,
+                      const uint32_t* order, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off,
+                      uint8_t* fwd_status, gd_key* target, uint64_t* out_total);
+int gd_forward_send(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uint32_t* out_silo, uint32_t* out_act,
+                    uint8_t* out_status, uint8_t* out_send_status, uint32_t* out_queue, uint32_t* out_perm,
+                    uint32_t* out_offsets, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off, uint8_t* fwd_status,
+                    gd_key* target, uint64_t* out_total);
+
 #ifdef __cplusplus
 }
 #endif

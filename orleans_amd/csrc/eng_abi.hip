@@ -129,6 +129,7 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->rsp_scr) free_buf(b);
     for (DevBuf& b : h->req_tab) free_buf(b);
     for (DevBuf& b : h->req_scr) free_buf(b);
+    for (DevBuf& b : h->fwd_scr) free_buf(b);
     for (DevBuf& b : h->col_scr) free_buf(b);
     for (DevBuf& b : h->stage_buf) free_buf(b);
     free_buf(h->up_last);

@@ -194,6 +194,9 @@ struct gd_handle {
     bool req_configured = false;
     DevBuf req_scr[4];                // plan records, output lengths, scanned offsets, the send stage's ttl
 
+    // forward writer (gd_forward.h, eng_forward.hip): the ActivationIds, silos and type names are the encoder's
+    DevBuf fwd_scr[5];                // plan records, output lengths, scanned offsets, the send stage's ttl and category
+
     // activation collector (gd_collect.h, eng_collect.hip): quantum and nextTicket in ticks (gd_collect_configure)
     int64_t col_quantum = 0, col_next = 0;   // col_quantum 0: not configured
     DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller

@@ -118,6 +118,8 @@ EXPORTED_SYMBOLS = [
     "gd_respond_frames_device", "gd_respond_frames",
     "gd_request_configure", "gd_request_frames_device", "gd_request_frames", "gd_request_send_device",
     "gd_request_send",
+    "gd_forward_kinds_device", "gd_forward_kinds", "gd_forward_frames_device", "gd_forward_frames",
+    "gd_forward_send_device", "gd_forward_send",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
@@ -297,6 +299,16 @@ class gd_request_batch(C.Structure):
                 ("generic", C.c_void_p), ("debug", C.c_void_p), ("id_base", C.c_int64), ("ttl_ticks", C.c_int64),
                 ("body", C.c_void_p), ("body_off", C.c_void_p)]
 
+
+class gd_forward_batch(C.Structure):
+    _fields_ = [("buf", C.c_void_p), ("buf_len", C.c_uint64), ("frame_off", C.c_void_p), ("kind", C.c_void_p),
+                ("old_act", C.c_void_p), ("fwd_silo", C.c_void_p), ("fwd_act", C.c_void_p),
+                ("max_forward_count", C.c_int32), ("local_silo", C.c_uint32)]
+
+
+GD_FWD_NONE, GD_FWD_FORWARD = 0, 1
+(GD_FWDST_OK_ADDRESSED, GD_FWDST_OK_UNADDRESSED, GD_FWDST_SKIPPED, GD_FWDST_MALFORMED, GD_FWDST_FALLBACK,
+ GD_FWDST_REJECT, GD_FWDST_NO_SILO, GD_FWDST_NO_ID) = range(8)
 
 GD_MULTI_RETURN_ROUTES = 1
 GD_MULTI_KEYS_READY = 2
@@ -483,6 +495,15 @@ def _load() -> C.CDLL:
         "gd_request_frames_device": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, U64, P, P]),
         "gd_request_frames": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, U64, P, P,
                                         C.POINTER(U64)]),
+        "gd_forward_kinds_device": (C.c_int, [P, P, U32, P]),
+        "gd_forward_kinds": (C.c_int, [P, P, U32, P]),
+        "gd_forward_frames_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P]),
+        "gd_forward_frames": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P,
+                                        C.POINTER(U64)]),
+        "gd_forward_send_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P,
+                                             P]),
+        "gd_forward_send": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P, P,
+                                      C.POINTER(U64)]),
         "gd_request_send_device": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, P, U64, P, P]),
         "gd_request_send": (C.c_int, [P, C.POINTER(gd_request_batch), U32, P, P, P, P, P, P, P, P, U64, P, P,
                                       C.POINTER(U64)]),
@@ -2662,6 +2683,93 @@ class GrainDispatch:
         self._c(lib.gd_request_send_device(self.h, C.byref(b), n, v(d_silo), v(d_act), v(d_status), v(d_send_status),
                                            v(d_queue), v(d_perm), v(d_offsets), v(d_out), out_cap, v(d_out_off),
                                            v(d_req_status)))
+
+    # -- forward writer (TryForwardRequest + AddressMessage + Message.Serialize) -------------------
+    def forward_kinds(self, turn):
+        """gd_forward_kinds: kind u8[n]."""
+        t = np.ascontiguousarray(np.asarray(turn, dtype=np.uint8))
+        kind = np.zeros(len(t), np.uint8)
+        self._c(lib.gd_forward_kinds(self.h, _ptr(t), len(t), _ptr(kind)))
+        return kind
+
+    def forward_kinds_device(self, d_turn: int, n: int, d_kind: int):
+        self._c(lib.gd_forward_kinds_device(self.h, C.c_void_p(d_turn), n, C.c_void_p(d_kind)))
+
+    def _forward_batch(self, buf: bytes, offsets, kind, old_act=None, fwd_silo=None, fwd_act=None,
+                       max_forward_count: int = 2, local_silo: int = 0):
+        """(gd_forward_batch with host pointers, n, the arrays it points at)."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        k = np.ascontiguousarray(np.asarray(kind, dtype=np.uint8))
+        oa, fs, fa = self._opt(old_act, np.uint32), self._opt(fwd_silo, np.uint32), self._opt(fwd_act, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        fb = gd_forward_batch(_ptr(b), len(buf), _ptr(off), _ptr(k), p(oa), p(fs), p(fa), max_forward_count,
+                              local_silo)
+        return fb, len(off), (b, off, k, oa, fs, fa)
+
+    def forward_frames(self, batch: dict, silo=None, act=None, status=None, placed=None, new_type=None, order=None,
+                       out_cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """gd_forward_frames: (out bytes u8[out_cap], out_off u64[n + 1], fwd_status u8[n], target u64[n, 3], total).
+        batch: the keyword arguments of _forward_batch."""
+        fb, n, keep = self._forward_batch(**batch)
+        sl, ac, st = self._opt(silo, np.uint32), self._opt(act, np.uint32), self._opt(status, np.uint8)
+        pl, nt, od = self._opt(placed, np.uint8), self._opt(new_type, np.uint32), self._opt(order, np.uint32)
+        if out is None:
+            out = np.zeros(2 * len(batch["buf"]) + n * 256 if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        fst = np.zeros(n, np.uint8)
+        target = np.zeros((n, 3), np.uint64)
+        total = C.c_uint64(0)
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_forward_frames(self.h, C.byref(fb), n, p(sl), p(ac), p(st), p(pl), p(nt), p(od),
+                                      _ptr(out) if len(out) else None, len(out), _ptr(out_off), _ptr(fst),
+                                      _ptr(target) if n else None, C.byref(total)))
+        return out, out_off, fst, target, int(total.value)
+
+    @staticmethod
+    def _forward_batch_device(d: dict):
+        v = lambda k: d.get(k) or None
+        return gd_forward_batch(v("buf"), d.get("buf_len", 0), v("frame_off"), v("kind"), v("old_act"), v("fwd_silo"),
+                                v("fwd_act"), d.get("max_forward_count", 2), d.get("local_silo", 0))
+
+    def forward_frames_device(self, d_batch: dict, n: int, d_silo: Optional[int], d_act: Optional[int],
+                              d_status: Optional[int], d_placed: Optional[int], d_new_type: Optional[int],
+                              d_order: Optional[int], d_out: int, out_cap: int, d_out_off: int, d_fwd_status: int,
+                              d_target: Optional[int]):
+        """d_batch: device addresses under _forward_batch's names, plus buf_len."""
+        fb = self._forward_batch_device(d_batch)
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_forward_frames_device(self.h, C.byref(fb), n, v(d_silo), v(d_act), v(d_status), v(d_placed),
+                                             v(d_new_type), v(d_order), v(d_out), out_cap, v(d_out_off),
+                                             v(d_fwd_status), v(d_target)))
+
+    def forward_send(self, batch: dict, out_cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> dict:
+        """gd_forward_send: plan + route + sender queues + writer; a dict of every stage's outputs."""
+        fb, n, keep = self._forward_batch(**batch)
+        silo, act, perm = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        status, sst, fst = np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        q = np.zeros(n, np.uint32)
+        offsets = np.zeros(getattr(self, "send_n_queues", 0) + 5, np.uint32)   # GD_ESTATE before send_configure
+        if out is None:
+            out = np.zeros(2 * len(batch["buf"]) + n * 256 if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        target = np.zeros((max(n, 1), 3), np.uint64)
+        total = C.c_uint64(0)
+        self._c(lib.gd_forward_send(self.h, C.byref(fb), n, _ptr(silo), _ptr(act), _ptr(status), _ptr(sst), _ptr(q),
+                                    _ptr(perm), _ptr(offsets), _ptr(out) if len(out) else None, len(out),
+                                    _ptr(out_off), _ptr(fst), _ptr(target), C.byref(total)))
+        return {"silo": silo, "act": act, "status": status, "send_status": sst, "queue": q, "perm": perm,
+                "offsets": offsets, "out": out, "out_off": out_off, "fwd_status": fst, "target": target[:n],
+                "total": int(total.value)}
+
+    def forward_send_device(self, d_batch: dict, n: int, d_silo: int, d_act: int, d_status: int, d_send_status: int,
+                            d_queue: Optional[int], d_perm: int, d_offsets: int, d_out: int, out_cap: int,
+                            d_out_off: int, d_fwd_status: int, d_target: int):
+        fb = self._forward_batch_device(d_batch)
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_forward_send_device(self.h, C.byref(fb), n, v(d_silo), v(d_act), v(d_status), v(d_send_status),
+                                           v(d_queue), v(d_perm), v(d_offsets), v(d_out), out_cap, v(d_out_off),
+                                           v(d_fwd_status), v(d_target)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
