@@ -2448,8 +2448,9 @@ int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uin
  * [out_off[offsets[q]], out_off[offsets[q + 1]]).  It returns the outputs of all three stages (d_queue may be
  * NULL; target is required); GD_ESTATE before gd_send_configure too.  Misses leave unaddressed: gd_route_place* on
  * the returned keys is the caller's next step.
- * Left to C#: the rejections of messages that may not forward, the cross-cluster return, system targets,
- * InvalidateCacheEntry on the receiving side, and FALLBACK frames. */
+ * Left to C#: the rejections of messages that may not forward, the cross-cluster return, system targets and
+ * FALLBACK frames.  InvalidateCacheEntry -- on the receiving side, and the sending side's own call for the old
+ * address (Dispatcher.cs:478, :497) -- is the sniff stage's (gd_sniff_invalidate*, gd_cache_invalidate*, below). */
 #define GD_FWD_NONE    0
 #define GD_FWD_FORWARD 1
 #define GD_FWDST_OK_ADDRESSED   0
@@ -2491,6 +2492,107 @@ int gd_forward_send(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uin
                     uint8_t* out_status, uint8_t* out_send_status, uint32_t* out_queue, uint32_t* out_perm,
                     uint32_t* out_offsets, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off, uint8_t* fwd_status,
                     gd_key* target, uint64_t* out_total);
+
+/* ---- sniff stage: SniffIncomingMessage + InvalidateCacheEntry for a batch --------------------------
+ * InsideRuntimeClient.SniffIncomingMessage (InsideRuntimeClient.cs:253-263) runs for every incoming message ahead of
+ * everything else: for each address of its CacheInvalidationHeader it calls LocalGrainDirectory.InvalidateCacheEntry
+ * (LocalGrainDirectory.cs:965-986): DirectoryCache.LookUp, then RemoveActivations(... t.Item2.Equals(activationId))
+ * (:1146-1164).  The stage does that for the frames of a received batch (buf, buf_len, frame_off[n], as
+ * gd_decode_frames) on the non-owner cache (gd_cache_configure).  No other entry point changes: gd_decode_frames*,
+ * gd_encode_frames* and gd_respond_frames* still answer FALLBACK for frames that carry the header.
+ *
+ * 1. gd_sniff_frames*: the entries.  The header is walked as the forward writer walks it: int32 count, then per entry
+ *    SiloAddress (24 B), GrainId UniqueKey (24 B + KeyExt string), ActivationId UniqueKey (24 B + KeyExt string).
+ *    Per frame i:
+ *      count[i]    entries the frame contributes; 0 without the header, and for a malformed frame.
+ *      ent_off[n + 1]  the exclusive prefix of count; ent_off[n] = m, the batch's entries.
+ *      status[i]   GD_SNIFF_NONE       mask bit 1 clear (the frame's length conditions hold);
+ *                  GD_SNIFF_OK         the header walked; a count of 0 is OK with no entries;
+ *                  GD_SNIFF_MALFORMED  the decoder's length conditions fail, the count is negative, a string length
+ *                                      is below -1, or an entry runs past the header.  No entries.
+ *      flags[i]    bit 0 (GD_SNIFF_FLAG_RETURNED) = the message's IsReturnedFromRemoteCluster as the reference's
+ *                  deserializer would leave it.  The reference gives that header no wire form: GetHeadersMask
+ *                  (Message.cs:1075-1117) never sets mask bit 25, the serializer writes no byte for it and the
+ *                  deserializer (:1247-1356) never reads it, so a received message's value is false and bit 0 is
+ *                  always 0.  A frame whose mask has bit 25 set is not one the reference's serializer wrote: it gets
+ *                  bit 1 (GD_SNIFF_FLAG_UNKNOWN), C# decides; no byte is guessed at.  0 for a malformed frame.
+ *    Per entry e in [ent_off[i], ent_off[i + 1]), in header order -- batch order x header order is the reference's
+ *    call order:
+ *      ent_frame[e]    i.
+ *      ent_silo[e]     the SiloAddress' 24 wire bytes as six dwords (gd_frame_fields' silo layout).
+ *      ent_grain[e]    the GrainId's three words.
+ *      ent_ext_off[e], ent_ext_len[e]  the GrainId's KeyExt string: its absolute offset into buf and its UTF-8 length,
+ *                      GD_KEYEXT_NULL for null.  The strings are not copied: {buf, ent_ext_off, ent_ext_len, buf_len}
+ *                      is a gd_key_ext of the entries.
+ *      ent_act_id[e]   the ActivationId's three words; all zeros for an ActivationId that carries a non-null KeyExt
+ *                      string (the map of gd_activation_ids_set holds null-KeyExt ids only, and by UniqueKey.Equals
+ *                      such an id equals none of them).
+ *    Any output but count, ent_off and status may be NULL.  ent_cap = the entries the entry arrays hold: if
+ *    m > ent_cap no entry is written, ent_off is still complete, and the handle's device error word is raised -- the
+ *    host form returns GD_EFULL, the device form reports it at the next checked synchronisation (gd_encode_frames'
+ *    rule).  n == 0 is GD_OK (ent_off[0] = 0).  Frames must be disjoint ranges of buf; an entry holds at least 80 B,
+ *    so m <= buf_len / 80, and a call with buf_len / 80 >= 2^32 is GD_EINVAL, as is n > 2^31.  GD_ESTATE inside a
+ *    hipGraph capture.
+ *
+ * 2. gd_cache_invalidate*: InvalidateCacheEntry(keys[k], act_ids[k]) for k = 0 .. m - 1 in order on the cache
+ *    (GD_ESTATE before gd_cache_configure).  ext (may be NULL) keys KeyExt grains by their string, as
+ *    gd_cache_lookup_ext.  The device form takes d_m (may be NULL): the live count on the device; the launch is sized
+ *    by m, the arrays' capacity, and entries at or past *d_m are not read, have no effect and get no out[k]; *d_m
+ *    above m (the sniff stage's GD_EFULL) processes nothing.  out[k]:
+ *      GD_INV_MISS     LookUp missed -- also a grain an earlier entry of this batch removed.  NumAccesses counted.
+ *      GD_INV_REMOVED  hit; the cached activation's ActivationId (gd_activation_ids_set) equals act_ids[k]: the entry
+ *                      is removed as gd_cache_remove removes (counters, tombstone).
+ *      GD_INV_KEPT     hit; another activation, or the cached empty list (silo GD_NO_SILO): the entry stays.
+ *      GD_INV_HOST     hit; the entry is GD_ACT_MULTI: its list is C#'s, the entry stays.
+ *      GD_INV_NO_ID    hit; the cached activation has no ActivationId in the map: the entry stays.
+ *    Every hit, the removing one included, is a LookUp hit (AdaptiveGrainDirectoryCache.cs:90-109): it takes the next
+ *    LRU generation in batch order and one NumAccesses++ on its entry, and accesses / hits of gd_cache_stats advance
+ *    as gd_cache_lookup advances them.  A key the device cannot match (GD_KEYEXT_HOST, a string range outside
+ *    bytes_len) is GD_INV_MISS without an access counted in the device form and GD_EINVAL (nothing done) in the host
+ *    form, as gd_cache_remove_ext treats it.  Not done here: invalidateDirectoryAlso -> registrar.InvalidateCache
+ *    (:981-985, multi-cluster) stays in C#, fed by flags; the entry's SiloAddress is not compared, because the
+ *    reference does not compare it.
+ *
+ * 3. gd_sniff_invalidate*: the chain, no host read-back in the device form: gd_sniff_frames, then
+ *    gd_cache_invalidate on (ent_grain, {buf, ent_ext_off, ent_ext_len}, ent_act_id) with d_m = ent_off + n and the
+ *    capacity ent_cap; inv[e] is entry e's GD_INV_*.  ent_grain, ent_ext_off, ent_ext_len, ent_act_id and inv are
+ *    required here (ent_cap > 0).  m > ent_cap: GD_EFULL as above and the cache is unchanged. */
+#define GD_SNIFF_NONE      0
+#define GD_SNIFF_OK        1
+#define GD_SNIFF_MALFORMED 2
+#define GD_SNIFF_FLAG_RETURNED 1
+#define GD_SNIFF_FLAG_UNKNOWN  2
+#define GD_INV_MISS    0
+#define GD_INV_REMOVED 1
+#define GD_INV_KEPT    2
+#define GD_INV_HOST    3
+#define GD_INV_NO_ID   4
+typedef struct gd_sniff_out {
+    uint32_t* count;        /* [n]                                                     */
+    uint32_t* ent_off;      /* [n + 1]                                                 */
+    uint8_t*  status;       /* [n] GD_SNIFF_*                                          */
+    uint8_t*  flags;        /* [n] GD_SNIFF_FLAG_*, or NULL                            */
+    uint32_t* ent_frame;    /* [ent_cap] or NULL                                       */
+    uint32_t* ent_silo;     /* [ent_cap * 6] or NULL                                   */
+    gd_key*   ent_grain;    /* [ent_cap] or NULL                                       */
+    uint64_t* ent_ext_off;  /* [ent_cap] or NULL                                       */
+    int32_t*  ent_ext_len;  /* [ent_cap] or NULL                                       */
+    gd_key*   ent_act_id;   /* [ent_cap] or NULL                                       */
+} gd_sniff_out;
+/* Device pointers (the out struct is a host struct of device pointers), enqueue only, no host read-back. */
+int gd_sniff_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                           uint32_t n, const gd_sniff_out* d_out, uint32_t ent_cap);
+int gd_cache_invalidate_device(gd_handle* h, const gd_key* d_keys, const gd_key_ext* d_ext, const gd_key* d_act_ids,
+                               uint32_t m, const uint32_t* d_m, uint8_t* d_out);
+int gd_sniff_invalidate_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len, const uint64_t* d_frame_off,
+                               uint32_t n, const gd_sniff_out* d_out, uint32_t ent_cap, uint8_t* d_inv);
+/* Host pointers, synchronous; *out_m (may be NULL) = ent_off[n].  Only the first m entries are written. */
+int gd_sniff_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                    const gd_sniff_out* out, uint32_t ent_cap, uint32_t* out_m);
+int gd_cache_invalidate(gd_handle* h, const gd_key* keys, const gd_key_ext* ext, const gd_key* act_ids, uint32_t m,
+                        uint8_t* out);
+int gd_sniff_invalidate(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
+                        const gd_sniff_out* out, uint32_t ent_cap, uint8_t* inv, uint32_t* out_m);
 
 #ifdef __cplusplus
 }

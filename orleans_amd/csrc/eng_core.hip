@@ -502,6 +502,8 @@ int report_device_error(gd_handle* h) {
         return set_err(h, GD_EINVAL, "an ActivationDirectory entry's context index is not below n_ctx");
     if (e == 128u)   // ERR_ENC_FULL (gd_frameout.h)
         return set_err(h, GD_EFULL, "gd_encode_frames: the encoded frames need more than out_cap bytes (out_off[n])");
+    if (e == 256u)   // ERR_SNIFF_FULL (gd_sniff.h)
+        return set_err(h, GD_EFULL, "gd_sniff_frames: the batch holds more than ent_cap entries (ent_off[n])");
     if (e & 2u) return set_err(h, GD_EFULL, "the directory table is full (device error bits 0x%x)", e);
     if (e & 4u)
         return set_err(h, GD_EINVAL, "a registration's silo index is above 0xFFFE (device error bits 0x%x)", e);

@@ -197,6 +197,11 @@ struct gd_handle {
     // forward writer (gd_forward.h, eng_forward.hip): the ActivationIds, silos and type names are the encoder's
     DevBuf fwd_scr[5];                // plan records, output lengths, scanned offsets, the send stage's ttl and category
 
+    // sniff stage (gd_sniff.h, eng_sniff.hip): InvalidateCacheEntry's first-matching-entry word a cache slot (NONE32
+    // between calls), the entries' slots, their classes
+    DevBuf inv_scr[3];
+    unsigned long long inv_cap = 0;   // the cache capacity inv_scr[0] is laid out (and all NONE32) for; 0: not
+
     // activation collector (gd_collect.h, eng_collect.hip): quantum and nextTicket in ticks (gd_collect_configure)
     int64_t col_quantum = 0, col_next = 0;   // col_quantum 0: not configured
     DevBuf col_scr[5];                // election words (NONE32 between calls); tile counts; verdicts when the caller

@@ -120,6 +120,8 @@ EXPORTED_SYMBOLS = [
     "gd_request_send",
     "gd_forward_kinds_device", "gd_forward_kinds", "gd_forward_frames_device", "gd_forward_frames",
     "gd_forward_send_device", "gd_forward_send",
+    "gd_sniff_frames_device", "gd_sniff_frames", "gd_cache_invalidate_device", "gd_cache_invalidate",
+    "gd_sniff_invalidate_device", "gd_sniff_invalidate",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
@@ -309,6 +311,19 @@ class gd_forward_batch(C.Structure):
 GD_FWD_NONE, GD_FWD_FORWARD = 0, 1
 (GD_FWDST_OK_ADDRESSED, GD_FWDST_OK_UNADDRESSED, GD_FWDST_SKIPPED, GD_FWDST_MALFORMED, GD_FWDST_FALLBACK,
  GD_FWDST_REJECT, GD_FWDST_NO_SILO, GD_FWDST_NO_ID) = range(8)
+
+
+
+class gd_sniff_out(C.Structure):
+    _fields_ = [("count", C.c_void_p), ("ent_off", C.c_void_p), ("status", C.c_void_p), ("flags", C.c_void_p),
+                ("ent_frame", C.c_void_p), ("ent_silo", C.c_void_p), ("ent_grain", C.c_void_p),
+                ("ent_ext_off", C.c_void_p), ("ent_ext_len", C.c_void_p), ("ent_act_id", C.c_void_p)]
+
+
+SNIFF_FIELDS = tuple(f for f, _ in gd_sniff_out._fields_)
+GD_SNIFF_NONE, GD_SNIFF_OK, GD_SNIFF_MALFORMED = range(3)
+GD_SNIFF_FLAG_RETURNED, GD_SNIFF_FLAG_UNKNOWN = 1, 2
+GD_INV_MISS, GD_INV_REMOVED, GD_INV_KEPT, GD_INV_HOST, GD_INV_NO_ID = range(5)
 
 GD_MULTI_RETURN_ROUTES = 1
 GD_MULTI_KEYS_READY = 2
@@ -500,6 +515,12 @@ def _load() -> C.CDLL:
         "gd_forward_frames_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P]),
         "gd_forward_frames": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P,
                                         C.POINTER(U64)]),
+        "gd_sniff_frames_device": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32]),
+        "gd_sniff_frames": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, C.POINTER(U32)]),
+        "gd_cache_invalidate_device": (C.c_int, [P, P, C.POINTER(gd_key_ext), P, U32, P, P]),
+        "gd_cache_invalidate": (C.c_int, [P, P, C.POINTER(gd_key_ext), P, U32, P]),
+        "gd_sniff_invalidate_device": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, P]),
+        "gd_sniff_invalidate": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, P, C.POINTER(U32)]),
         "gd_forward_send_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P,
                                              P]),
         "gd_forward_send": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P, P,
@@ -2770,6 +2791,92 @@ class GrainDispatch:
         self._c(lib.gd_forward_send_device(self.h, C.byref(fb), n, v(d_silo), v(d_act), v(d_status), v(d_send_status),
                                            v(d_queue), v(d_perm), v(d_offsets), v(d_out), out_cap, v(d_out_off),
                                            v(d_fwd_status), v(d_target)))
+
+    # -- sniff stage (SniffIncomingMessage + InvalidateCacheEntry) -------------------------------
+    @staticmethod
+    def _sniff_host(n: int, ent_cap: int):
+        """(gd_sniff_out with host pointers, the arrays it points at by field name)."""
+        a = {"count": np.zeros(n, np.uint32), "ent_off": np.zeros(n + 1, np.uint32), "status": np.zeros(n, np.uint8),
+             "flags": np.zeros(n, np.uint8), "ent_frame": np.zeros(ent_cap, np.uint32),
+             "ent_silo": np.zeros((ent_cap, 6), np.uint32), "ent_grain": np.zeros((ent_cap, 3), np.uint64),
+             "ent_ext_off": np.zeros(ent_cap, np.uint64), "ent_ext_len": np.zeros(ent_cap, np.int32),
+             "ent_act_id": np.zeros((ent_cap, 3), np.uint64)}
+        one = np.zeros(4, np.uint64)                           # what an empty array's pointer stands on
+        return gd_sniff_out(*[_ptr(a[f]) if a[f].size else _ptr(one) for f in SNIFF_FIELDS]), dict(a, _one=one)
+
+    @staticmethod
+    def _sniff_result(a: dict, m: int) -> dict:
+        out = {f: (v[:m] if f.startswith("ent_") and f != "ent_off" else v) for f, v in a.items() if f != "_one"}
+        out["m"] = m
+        return out
+
+    def sniff_frames(self, buf: bytes, offsets, ent_cap: Optional[int] = None) -> dict:
+        """gd_sniff_frames: the per-frame arrays, the first m entries of the per-entry arrays, and m.
+        ent_cap None: len(buf) // 80, the most a buffer can hold."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        cap = len(buf) // 80 if ent_cap is None else ent_cap
+        so, a = self._sniff_host(n, cap)
+        m = C.c_uint32(0)
+        try:
+            self._c(lib.gd_sniff_frames(self.h, _ptr(b), len(buf), _ptr(off) if n else None, n, C.byref(so), cap,
+                                        C.byref(m)))
+        except GrainDispatchError as ex:                       # GD_EFULL: ent_off is complete, the entry arrays untouched
+            ex.arrays = a
+            raise
+        return self._sniff_result(a, int(m.value))
+
+    def sniff_frames_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, d_out: dict, ent_cap: int):
+        """d_out: device addresses under gd_sniff_out's field names (absent or None: not wanted)."""
+        so = gd_sniff_out(*[d_out.get(f) or None for f in SNIFF_FIELDS])
+        self._c(lib.gd_sniff_frames_device(self.h, C.c_void_p(d_buf or 0), buf_len, C.c_void_p(d_offsets or 0), n,
+                                           C.byref(so), ent_cap))
+
+    def cache_invalidate(self, keys, act_ids, exts=None) -> np.ndarray:
+        """gd_cache_invalidate: InvalidateCacheEntry(keys[k], act_ids[k]) in order; out u8[m] of GD_INV_*."""
+        k, ids = keys_array(keys), keys_array(act_ids)
+        m = len(k)
+        assert len(ids) == m, "one ActivationId per key"
+        out = np.zeros(m, np.uint8)
+        x = None if exts is None else self._ext(exts, m)
+        self._c(lib.gd_cache_invalidate(self.h, _ptr(k), None if x is None else C.byref(x.struct), _ptr(ids), m,
+                                        _ptr(out)))
+        return out
+
+    def cache_invalidate_device(self, d_keys: int, d_ext: Optional[dict], d_act_ids: int, m: int, d_m: Optional[int],
+                                d_out: int):
+        """d_ext: {"bytes", "offset", "length", "bytes_len"} of device addresses, or None."""
+        dx = None if d_ext is None else gd_key_ext(d_ext.get("bytes") or None, d_ext["offset"], d_ext["length"],
+                                                   d_ext.get("bytes_len", 0))
+        v = lambda a: C.c_void_p(a or 0)
+        self._c(lib.gd_cache_invalidate_device(self.h, v(d_keys), None if dx is None else C.byref(dx), v(d_act_ids), m,
+                                               v(d_m), v(d_out)))
+
+    def sniff_invalidate(self, buf: bytes, offsets, ent_cap: Optional[int] = None) -> dict:
+        """gd_sniff_invalidate: sniff_frames' dict plus "inv" u8[m] of GD_INV_*."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        cap = len(buf) // 80 if ent_cap is None else ent_cap
+        so, a = self._sniff_host(n, cap)
+        inv = np.zeros(cap, np.uint8)
+        m = C.c_uint32(0)
+        try:
+            self._c(lib.gd_sniff_invalidate(self.h, _ptr(b), len(buf), _ptr(off) if n else None, n, C.byref(so), cap,
+                                            _ptr(inv) if cap else None, C.byref(m)))
+        except GrainDispatchError as ex:
+            ex.arrays = dict(a, inv=inv)
+            raise
+        out = self._sniff_result(a, int(m.value))
+        out["inv"] = inv[:out["m"]]
+        return out
+
+    def sniff_invalidate_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, d_out: dict, ent_cap: int,
+                                d_inv: int):
+        so = gd_sniff_out(*[d_out.get(f) or None for f in SNIFF_FIELDS])
+        self._c(lib.gd_sniff_invalidate_device(self.h, C.c_void_p(d_buf or 0), buf_len, C.c_void_p(d_offsets or 0), n,
+                                               C.byref(so), ent_cap, C.c_void_p(d_inv or 0)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
