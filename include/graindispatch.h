@@ -2594,6 +2594,146 @@ int gd_cache_invalidate(gd_handle* h, const gd_key* keys, const gd_key_ext* ext,
 int gd_sniff_invalidate(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
                         const gd_sniff_out* out, uint32_t ent_cap, uint8_t* inv, uint32_t* out_m);
 
+/* ---- batched Catalog.GetOrCreateActivation: activations for a received batch ------------
+ * A message gd_receive* leaves GD_RECV_NULL_CONTEXT met no Valid activation.  Its closure
+ * (Dispatcher.ReceiveMessage, Core/Dispatcher.cs:75-201) first tests IsExpired (:79-85), then runs
+ * Catalog.GetOrCreateActivation (Catalog/Catalog.cs:443-518) under lock (activations): TryGetActivationData finds
+ * the activation in whatever state; or a dummy ActivationData is created and recorded (RegisterMessageTarget ->
+ * ActivationDirectory.RecordNewTarget, Catalog/ActivationDirectory.cs:86-93) when the message carries
+ * IsNewPlacement; or NonExistentActivationException leads to ProcessRequestToInvalidActivation +
+ * UnregisterAfterNonexistingActivation (requests) or InvalidateCacheEntry (responses).  gd_activate* is that step
+ * for a batch in arrival order, on the activation directory of gd_actdir_*.  (The reference runs these closures on
+ * the null context in no fixed order; arrival order is the batch model, as for every stage of this library.)
+ *
+ * Per message: ctx and recv_status as gd_receive* gave them; target_grain (not read: C# builds the ActivationData
+ * from it through new_idx) and target_activation; direction (NULL = every message a Request, 0xFF = absent =
+ * Request); ttl (NULL = none, GD_TTL_NONE = no value); new_placement (NULL = all 0; Message.IsNewPlacement, true
+ * only for the value 1).  Scalars: terminating = SiloStatusOracle.CurrentStatus.IsTerminating() (nothing is
+ * created); ctx_base and new_ctx[cap_new] (NULL: ctx_base + k), the contexts offered to new activations.
+ *
+ * Only messages with recv_status == GD_RECV_NULL_CONTEXT take part; every other message gets GD_ACTV_NONE and its
+ * ctx / status are copied through.  Per participating message, one by one in array order:
+ *   1. ttl has a value and is <= 0: GD_ACTV_EXPIRED; no state is touched.
+ *   2. the ActivationId is in the directory as an activation entry, in any state -- there before the batch or
+ *      created by an earlier message of it: GD_ACTV_FOUND, ctx_out = its context, status_out = GD_RECV_ACTIVATION.
+ *      A stored context >= n_ctx: GD_ACTV_HOST and the call fails with GD_EINVAL, as gd_receive's.
+ *   3. present only as a system-target entry: GD_ACTV_HOST (the reference keeps two dictionaries, the library one
+ *      table; C# handles this corner).
+ *   4. absent, new_placement set, not terminating: a candidate.  The k-th candidate of the batch (arrival order)
+ *      proposes new_ctx[k], or ctx_base + k.  The first candidate of an ActivationId creates the entry {its
+ *      proposal, flags 0}: not Valid, no system target, no stateless worker -- ActivationState.Create.  It gets
+ *      GD_ACTV_CREATED, ctx_out = the proposal, status_out = GD_RECV_ACTIVATION.  Later candidates of the id fall
+ *      under rule 2, so the proposals are sparse, as gd_route_place's.  *n_proposed = the candidates; new_idx
+ *      lists the creating messages in arrival order (C# builds an ActivationData for each and runs
+ *      SetupActivationInstance / InitActivation).
+ *   5. otherwise GD_ACTV_NONEXISTENT (Request, OneWay) or GD_ACTV_NONEXISTENT_RESPONSE; ctx / status copied
+ *      through.  gone_idx lists the GD_ACTV_NONEXISTENT messages in arrival order: the input of gd_forward_* and
+ *      the UnregisterAfterNonexistingActivation list.
+ * The batch is refused whole -- nothing is created, every participating message rules 1-3 do not decide gets
+ * GD_ACTV_HOST, n_new = n_gone = 0 -- when *n_proposed > cap_new or one of the first cap_new proposals is >= n_ctx.
+ * The host form then returns GD_EINVAL after writing the outputs; the device form's caller compares the
+ * n_proposed word with cap_new (gd_callbacks_expire's convention), and a proposal out of range fails the next
+ * synchronising call with GD_EINVAL, as gd_receive's context check.  new_ctx NULL and ctx_base + cap_new > n_ctx:
+ * GD_EINVAL up front.
+ *
+ * Outputs: kind[n]; ctx_out[n] / status_out[n], which may be the inputs ctx / recv_status; new_idx[n] with the word
+ * n_new and gone_idx[n] with n_gone, each both or neither; the word n_proposed.  The words are device words in
+ * the device form and host words in the host form.  The device form only enqueues: room for min(n, cap_new) new
+ * entries is reserved first, from a bound kept on the host, with one counter read-back (GD_ESTATE inside a
+ * capture) only when the bound cannot tell; its claims run a fixed number of gated passes, and a batch they do not
+ * settle fails the next synchronising call with GD_ETIMEOUT, as gd_callbacks_add_device's.  The host form is
+ * synchronous, GD_ESTATE inside a capture.
+ *
+ * Left to C#: GetGrainTypeInfo, the NewGrainType / GenericGrainType strings, the ActivationData object and
+ * InitActivation for new_idx, the later gd_actdir_set_flags(GD_ACTDIR_VALID), statistics and logging. */
+#define GD_ACTV_NONE                 0
+#define GD_ACTV_FOUND                1
+#define GD_ACTV_CREATED              2
+#define GD_ACTV_EXPIRED              3
+#define GD_ACTV_HOST                 4
+#define GD_ACTV_NONEXISTENT          5
+#define GD_ACTV_NONEXISTENT_RESPONSE 6
+int gd_activate_device(gd_handle* h, const uint32_t* d_ctx, const uint8_t* d_recv_status, const gd_key* d_target_grain,
+                       const gd_key* d_target_activation, const uint8_t* d_direction, const int64_t* d_ttl,
+                       const uint8_t* d_new_placement, uint32_t n, uint32_t n_ctx, int terminating, uint32_t ctx_base,
+                       const uint32_t* d_new_ctx, uint32_t cap_new, uint8_t* d_kind, uint32_t* d_ctx_out,
+                       uint8_t* d_status_out, uint32_t* d_new_idx, uint32_t* d_n_new, uint32_t* d_gone_idx,
+                       uint32_t* d_n_gone, uint32_t* d_n_proposed);
+int gd_activate(gd_handle* h, const uint32_t* ctx, const uint8_t* recv_status, const gd_key* target_grain,
+                const gd_key* target_activation, const uint8_t* direction, const int64_t* ttl,
+                const uint8_t* new_placement, uint32_t n, uint32_t n_ctx, int terminating, uint32_t ctx_base,
+                const uint32_t* new_ctx, uint32_t cap_new, uint8_t* out_kind, uint32_t* out_ctx, uint8_t* out_status,
+                uint32_t* out_new_idx, uint32_t* out_n_new, uint32_t* out_gone_idx, uint32_t* out_n_gone,
+                uint32_t* out_n_proposed);
+/* The chains: gd_receive_device -> gd_activate_device -> gd_turns_device on the resolved ctx / status (written in
+ * place into d_ctx / d_status), no host round trip.  The arguments are gd_receive_turns*'s, then the activation
+ * stage's in a struct (device pointers in the device forms, host pointers in the host forms; kind and n_proposed
+ * required).
+ *   - d_perm / d_offsets, when asked for, are the stable bucketing of the RESOLVED contexts: a message that found
+ *     or created its activation lies in that context's bucket in arrival order, not in the null bucket.
+ *   - The caller pre-fills state->ctx_flags = GD_CTX_NOT_READY, num_running = 0 and request_count = 0 for every
+ *     context it offers in new_ctx / ctx_base...  The turn stage (unchanged) then gives a created activation's
+ *     requests GD_TURN_WAIT, in order on its waiting list; a found Invalid one's requests FORWARD /
+ *     REJECT_TRANSIENT and its responses RESPONSE / RESPONSE_DROPPED.
+ *   - state->hard_limit or hard_limit_stateless_worker > 0: GD_EINVAL.  A null-context closure is enqueued with
+ *     a null target, so IncrementEnqueuedOnDispatcherCount never ran for it (IncomingMessageAgent.cs:172-190),
+ *     while the turn stage's closed form for EnqueueRequest's hard limit takes every participating message as
+ *     counted.  The reference's default is 0 (SiloMessagingOptions.cs:48-67).  With limits on, use gd_activate*
+ *     alone and leave those messages' turn to C#.
+ *   - frame-fed forms: new_placement is not read; Message.IsNewPlacement comes from the GD_RECV_NULL_CONTEXT
+ *     frames themselves (mask bit 18 set and the token SerializationTokenType.True).  A frame left
+ *     GD_RECV_UNDECODED never takes part.  ttl_age_ticks and d_msg_flags_or as gd_receive_turns_frames*; rule 1
+ *     reads the aged ttl.
+ *   - a refused batch: the turn stage still runs (the GD_ACTV_HOST messages keep GD_RECV_NULL_CONTEXT and get
+ *     GD_TURN_NONE); the host forms return GD_EINVAL after writing every output. */
+typedef struct gd_activate_io {
+    const uint8_t*  new_placement;   /* [n] or NULL (array-fed forms)                       */
+    int32_t         terminating;
+    uint32_t        ctx_base;
+    const uint32_t* new_ctx;         /* [cap_new] or NULL                                   */
+    uint32_t        cap_new;
+    uint8_t*        kind;            /* [n] GD_ACTV_*                                       */
+    uint32_t*       new_idx;         /* [n] with n_new, or both NULL                        */
+    uint32_t*       n_new;
+    uint32_t*       gone_idx;        /* [n] with n_gone, or both NULL                       */
+    uint32_t*       n_gone;
+    uint32_t*       n_proposed;
+} gd_activate_io;
+int gd_receive_activate_turns_device(gd_handle* h, const gd_key* d_target_grain, const gd_key* d_target_activation,
+                                     const uint8_t* d_direction, uint32_t n, uint32_t n_ctx,
+                                     const gd_recv_limits* recv_limits, uint32_t* d_ctx, uint8_t* d_status,
+                                     uint32_t* d_perm, uint32_t* d_offsets, const int64_t* d_ttl,
+                                     const uint8_t* d_forward_count, const uint8_t* d_msg_flags,
+                                     const gd_key* d_sending_activation, const gd_turn_state* state, uint8_t* d_turn,
+                                     uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
+                                     uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets,
+                                     const gd_activate_io* d_act);
+int gd_receive_activate_turns(gd_handle* h, const gd_key* target_grain, const gd_key* target_activation,
+                              const uint8_t* direction, uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                              uint32_t* out_ctx, uint8_t* out_status, uint32_t* out_perm, uint32_t* out_offsets,
+                              const int64_t* ttl, const uint8_t* forward_count, const uint8_t* msg_flags,
+                              const gd_key* sending_activation, const gd_turn_state* state, uint8_t* out_turn,
+                              uint32_t* out_num_running, uint32_t* out_running_idx, uint32_t* out_start_idx,
+                              uint32_t* out_n_start, uint32_t* out_wait_perm, uint32_t* out_wait_offsets,
+                              const gd_activate_io* act);
+int gd_receive_activate_turns_frames_device(gd_handle* h, const uint8_t* d_buf, uint64_t buf_len,
+                                            const uint64_t* d_frame_off, uint32_t n, uint32_t n_ctx,
+                                            const gd_recv_limits* recv_limits, const gd_frame_fields* d_out,
+                                            const gd_frame_turn_fields* d_turn_out, uint32_t* d_ctx, uint8_t* d_status,
+                                            uint32_t* d_perm, uint32_t* d_offsets, int64_t ttl_age_ticks,
+                                            const uint8_t* d_msg_flags_or, const gd_turn_state* state, uint8_t* d_turn,
+                                            uint32_t* d_num_running_out, uint32_t* d_running_idx, uint32_t* d_start_idx,
+                                            uint32_t* d_n_start, uint32_t* d_wait_perm, uint32_t* d_wait_offsets,
+                                            const gd_activate_io* d_act);
+int gd_receive_activate_turns_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off,
+                                     uint32_t n, uint32_t n_ctx, const gd_recv_limits* recv_limits,
+                                     const gd_frame_fields* out, const gd_frame_turn_fields* turn_out, uint32_t* out_ctx,
+                                     uint8_t* out_status, uint32_t* out_perm, uint32_t* out_offsets,
+                                     int64_t ttl_age_ticks, const uint8_t* msg_flags_or, const gd_turn_state* state,
+                                     uint8_t* out_turn, uint32_t* out_num_running, uint32_t* out_running_idx,
+                                     uint32_t* out_start_idx, uint32_t* out_n_start, uint32_t* out_wait_perm,
+                                     uint32_t* out_wait_offsets, const gd_activate_io* act);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,7 +303,9 @@ int receive_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const 
 int ad_pull(gd_handle* h) {
     GD_TRY(fold_counters(h, h->ad_ctr));
     HIP_TRY(h, hipMemcpyAsync(&h->ad_host, h->ad_ctr, sizeof(DevCounters), hipMemcpyDeviceToHost, h->stream));
-    return sync(h);
+    GD_TRY(sync(h));
+    h->ad_used_ub = h->ad_host.live + h->ad_host.tomb;   // gd_activate*'s bound (table_reserve)
+    return GD_OK;
 }
 
 // (Re)build the ActivationDirectory table with cap slots (tombstones dropped).

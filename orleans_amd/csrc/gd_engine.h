@@ -145,6 +145,10 @@ struct gd_handle {
     DevBuf fr_recv[3];                // frames: TargetActivation / Direction scratch when the caller wants neither
     DevBuf frt_scr[8];                // gd_receive_turns_frames*: the decoded fields the caller did not ask back
     DevBuf recv_scr[2];               // receive with limits but no buckets wanted: perm / offsets scratch
+    // activation stage (gd_activate.h, eng_activate.hip)
+    uint64_t ad_used_ub = 0;          // live + tombstones at most: the last ad_pull plus every possible creation since
+    DevBuf actv_scr[10];              // tile counts (candidates, created, gone); candidates' idx, keys, proposals,
+                                      // slot_of, is_new; the call's words; the frame-fed chain's IsNewPlacement bytes
 
     // sender queues (gd_sendq.h, eng_send.hip): the per-silo application bucket (gd_send_configure)
     DevBuf send_tab;
@@ -234,11 +238,11 @@ struct gd_handle {
     DevBuf cls_wide, cls_silo;
 
     // The host-pointer forms of the six stages above and the collector's stage their inputs and outputs here, through HostStage
-    // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_receive_turns_frames).
+    // (below): the k-th array of a call takes slot k; STAGE_SLOTS is the widest call's need (gd_receive_activate_turns_frames).
     // One pool serves them all: each of these calls synchronises the stream before it returns and none reads
     // what an earlier one staged; a call that returned early on an error left its work on the same stream,
     // ahead of the next call's, and ensure() synchronises before it frees a slot to grow it.
-    static constexpr uint32_t STAGE_SLOTS = 36;
+    static constexpr uint32_t STAGE_SLOTS = 46;
     DevBuf stage_buf[STAGE_SLOTS];
 
     // KeyExt grains (gd_keyext.h): device table + heap, and the host index both are kept from
@@ -576,6 +580,30 @@ int cx_reserve(gd_handle* h, uint64_t need);
 int ad_reserve(gd_handle* h, uint64_t incoming);
 int ad_pull(gd_handle* h);
 int ad_rehash(gd_handle* h, unsigned long long cap);
+// The activation stage on device arrays (eng_activate.hip); the chained forms call it between the receive and the
+// turn stage (eng_turns.hip).
+struct ActivateArgs {
+    const uint32_t* ctx;
+    const uint8_t* recv_status;
+    const gd_key* target_activation;
+    const uint8_t* direction;
+    const int64_t* ttl;
+    const uint8_t* new_placement;
+    int64_t ttl_age;
+    uint32_t n, n_ctx;
+    int terminating;
+    uint32_t ctx_base;
+    const uint32_t* new_ctx;
+    uint32_t cap_new;
+    uint8_t* kind;
+    uint32_t* ctx_out;
+    uint8_t* status_out;
+    uint32_t *new_idx, *n_new, *gone_idx, *n_gone, *n_proposed;
+};
+int check_activate_args(gd_handle* h, const ActivateArgs& a, const char* call);
+int activate_device(gd_handle* h, const ActivateArgs& a, bool host_form, bool* refused, const char* call);
+int frame_new_placement_device(gd_handle* h, const uint8_t* buf, uint64_t len, const uint64_t* off, const uint8_t* st,
+                               uint32_t n, const uint8_t** out);
 int fan_args_ok(gd_handle* h, const uint32_t* row_off, const uint32_t* dst, uint32_t nf, const uint32_t* frontier,
                 uint64_t* out_n);
 int fan_route(gd_handle* h, const uint32_t* row_off, const uint32_t* dst, const uint32_t* frontier, uint32_t nf,

@@ -122,6 +122,8 @@ EXPORTED_SYMBOLS = [
     "gd_forward_send_device", "gd_forward_send",
     "gd_sniff_frames_device", "gd_sniff_frames", "gd_cache_invalidate_device", "gd_cache_invalidate",
     "gd_sniff_invalidate_device", "gd_sniff_invalidate",
+    "gd_activate_device", "gd_activate", "gd_receive_activate_turns_device", "gd_receive_activate_turns",
+    "gd_receive_activate_turns_frames_device", "gd_receive_activate_turns_frames",
     "gd_collect_configure", "gd_collect_next_ticket", "gd_collect_schedule_device", "gd_collect_schedule",
     "gd_collect_cancel_device", "gd_collect_cancel", "gd_collect_touch_device", "gd_collect_touch",
     "gd_collect_idle_device", "gd_collect_idle", "gd_collect_scan_stale_device", "gd_collect_scan_stale",
@@ -325,6 +327,16 @@ GD_SNIFF_NONE, GD_SNIFF_OK, GD_SNIFF_MALFORMED = range(3)
 GD_SNIFF_FLAG_RETURNED, GD_SNIFF_FLAG_UNKNOWN = 1, 2
 GD_INV_MISS, GD_INV_REMOVED, GD_INV_KEPT, GD_INV_HOST, GD_INV_NO_ID = range(5)
 
+
+class gd_activate_io(C.Structure):
+    _fields_ = [("new_placement", C.c_void_p), ("terminating", C.c_int32), ("ctx_base", C.c_uint32),
+                ("new_ctx", C.c_void_p), ("cap_new", C.c_uint32), ("kind", C.c_void_p), ("new_idx", C.c_void_p),
+                ("n_new", C.c_void_p), ("gone_idx", C.c_void_p), ("n_gone", C.c_void_p), ("n_proposed", C.c_void_p)]
+
+
+(GD_ACTV_NONE, GD_ACTV_FOUND, GD_ACTV_CREATED, GD_ACTV_EXPIRED, GD_ACTV_HOST, GD_ACTV_NONEXISTENT,
+ GD_ACTV_NONEXISTENT_RESPONSE) = range(7)
+
 GD_MULTI_RETURN_ROUTES = 1
 GD_MULTI_KEYS_READY = 2
 GD_MULTI_FORWARD = 4
@@ -521,6 +533,22 @@ def _load() -> C.CDLL:
         "gd_cache_invalidate": (C.c_int, [P, P, C.POINTER(gd_key_ext), P, U32, P]),
         "gd_sniff_invalidate_device": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, P]),
         "gd_sniff_invalidate": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, P, C.POINTER(U32)]),
+        "gd_activate_device": (C.c_int, [P] + [P] * 7 + [U32, U32, C.c_int, U32, P, U32] + [P] * 8),
+        "gd_activate": (C.c_int, [P] + [P] * 7 + [U32, U32, C.c_int, U32, P, U32] + [P] * 8),
+        "gd_receive_activate_turns_device": (C.c_int, [P, P, P, P, U32, U32, C.POINTER(gd_recv_limits), P, P, P, P, P,
+                                                       P, P, P, C.POINTER(gd_turn_state)] + [P] * 7 +
+                                             [C.POINTER(gd_activate_io)]),
+        "gd_receive_activate_turns": (C.c_int, [P, P, P, P, U32, U32, C.POINTER(gd_recv_limits), P, P, P, P, P, P, P, P,
+                                                C.POINTER(gd_turn_state)] + [P] * 7 + [C.POINTER(gd_activate_io)]),
+        "gd_receive_activate_turns_frames_device": (C.c_int, [P, P, U64, P, U32, U32, C.POINTER(gd_recv_limits),
+                                                              C.POINTER(gd_frame_fields),
+                                                              C.POINTER(gd_frame_turn_fields), P, P, P, P, C.c_int64, P,
+                                                              C.POINTER(gd_turn_state)] + [P] * 7 +
+                                                    [C.POINTER(gd_activate_io)]),
+        "gd_receive_activate_turns_frames": (C.c_int, [P, P, U64, P, U32, U32, C.POINTER(gd_recv_limits),
+                                                       C.POINTER(gd_frame_fields), C.POINTER(gd_frame_turn_fields),
+                                                       P, P, P, P, C.c_int64, P, C.POINTER(gd_turn_state)] + [P] * 7 +
+                                             [C.POINTER(gd_activate_io)]),
         "gd_forward_send_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P,
                                              P]),
         "gd_forward_send": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, P, U64, P, P, P,
@@ -2877,6 +2905,171 @@ class GrainDispatch:
         so = gd_sniff_out(*[d_out.get(f) or None for f in SNIFF_FIELDS])
         self._c(lib.gd_sniff_invalidate_device(self.h, C.c_void_p(d_buf or 0), buf_len, C.c_void_p(d_offsets or 0), n,
                                                C.byref(so), ent_cap, C.c_void_p(d_inv or 0)))
+
+    # -- batched Catalog.GetOrCreateActivation -----------------------------------------
+    def activate(self, ctx, recv_status, target_activation, n_ctx: int, cap_new: int, ctx_base: int = 0, new_ctx=None,
+                 direction=None, ttl=None, new_placement=None, terminating: bool = False, target_grain=None,
+                 lists: bool = True) -> dict:
+        """gd_activate: kind u8, ctx u32, status u8, n_proposed[, new_idx u32[n_new], gone_idx u32[n_gone]].  A
+        refused batch raises GD_EINVAL with the outputs in the error's `arrays`."""
+        c = np.ascontiguousarray(np.asarray(ctx, dtype=np.uint32))
+        n = len(c)
+        rs = np.ascontiguousarray(np.asarray(recv_status, dtype=np.uint8))
+        ta = keys_array(target_activation)
+        tg = None if target_grain is None else keys_array(target_grain)
+        dr, tl = self._opt(direction, np.uint8), self._opt(ttl, np.int64)
+        npl, nc = self._opt(new_placement, np.uint8), self._opt(new_ctx, np.uint32)
+        kind, co, so = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        new_idx = np.zeros(max(n, 1), np.uint32) if lists else None
+        gone_idx = np.zeros(max(n, 1), np.uint32) if lists else None
+        words = np.zeros(3, np.uint32)                       # n_new, n_gone, n_proposed
+        p = lambda a: None if a is None else _ptr(a)
+        w = lambda k: words.ctypes.data + 4 * k
+
+        def result():
+            out = dict(kind=kind, ctx=co, status=so, n_proposed=int(words[2]))
+            if lists:
+                out.update(new_idx=new_idx[:int(words[0])].copy(), gone_idx=gone_idx[:int(words[1])].copy())
+            return out
+        try:
+            self._c(lib.gd_activate(self.h, _ptr(c), _ptr(rs), p(tg), _ptr(ta), p(dr), p(tl), p(npl), n, n_ctx,
+                                    int(terminating), ctx_base, p(nc), cap_new, _ptr(kind), _ptr(co), _ptr(so),
+                                    p(new_idx), w(0) if lists else None, p(gone_idx), w(1) if lists else None, w(2)))
+        except GrainDispatchError as ex:
+            ex.arrays = result()
+            raise
+        return result()
+
+    def activate_device(self, d_ctx: int, d_recv_status: int, d_target_activation: int, n: int, n_ctx: int,
+                        cap_new: int, d_kind: int, d_ctx_out: int, d_status_out: int, d_n_proposed: int,
+                        ctx_base: int = 0, d_new_ctx: Optional[int] = None, d_direction: Optional[int] = None,
+                        d_ttl: Optional[int] = None, d_new_placement: Optional[int] = None, terminating: bool = False,
+                        d_new_idx: Optional[int] = None, d_n_new: Optional[int] = None,
+                        d_gone_idx: Optional[int] = None, d_n_gone: Optional[int] = None,
+                        d_target_grain: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_activate_device(self.h, V(d_ctx), V(d_recv_status), V(d_target_grain), V(d_target_activation),
+                                       V(d_direction), V(d_ttl), V(d_new_placement), n, n_ctx, int(terminating),
+                                       ctx_base, V(d_new_ctx), cap_new, V(d_kind), V(d_ctx_out), V(d_status_out),
+                                       V(d_new_idx), V(d_n_new), V(d_gone_idx), V(d_n_gone), V(d_n_proposed)))
+
+    @staticmethod
+    def activate_io_device(cap_new: int, d_kind: int, d_n_proposed: int, ctx_base: int = 0,
+                           d_new_ctx: Optional[int] = None, d_new_placement: Optional[int] = None,
+                           terminating: bool = False, d_new_idx: Optional[int] = None, d_n_new: Optional[int] = None,
+                           d_gone_idx: Optional[int] = None, d_n_gone: Optional[int] = None) -> gd_activate_io:
+        return gd_activate_io(d_new_placement or None, int(terminating), ctx_base, d_new_ctx or None, cap_new,
+                              d_kind or None, d_new_idx or None, d_n_new or None, d_gone_idx or None, d_n_gone or None,
+                              d_n_proposed or None)
+
+    def _activate_io_host(self, n, cap_new, ctx_base, new_ctx, new_placement, terminating):
+        """(gd_activate_io with host pointers, result(), the arrays kept alive)."""
+        npl, nc = self._opt(new_placement, np.uint8), self._opt(new_ctx, np.uint32)
+        kind = np.zeros(n, np.uint8)
+        new_idx, gone_idx = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        words = np.zeros(3, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        w = lambda k: words.ctypes.data + 4 * k
+        io = gd_activate_io(p(npl), int(terminating), ctx_base, p(nc), cap_new, _ptr(kind), _ptr(new_idx), w(0),
+                            _ptr(gone_idx), w(1), w(2))
+        result = lambda: dict(kind=kind, new_idx=new_idx[:int(words[0])].copy(),
+                              gone_idx=gone_idx[:int(words[1])].copy(), n_proposed=int(words[2]))
+        return io, result, (npl, nc, kind, new_idx, gone_idx, words)
+
+    def receive_activate_turns(self, target_grain, target_activation, n_ctx: int, ctx_flags, num_running,
+                               request_count, cap_new: int, ctx_base: int = 0, new_ctx=None, new_placement=None,
+                               terminating: bool = False, direction=None, ttl=None, forward_count=None, msg_flags=None,
+                               sending_activation=None, hard_limit: int = 0, hard_limit_sw: int = 0,
+                               max_forward_count: int = 2, chain: bool = False) -> dict:
+        """gd_receive_activate_turns: activate()'s dict (ctx / status resolved) plus perm, offsets[n_ctx + 3], turn,
+        num_running_out, running_idx, start_idx, wait_perm, wait_offsets[n_ctx + 2]."""
+        tg, ta = keys_array(target_grain), keys_array(target_activation)
+        n = len(tg)
+        sa = None if sending_activation is None else keys_array(sending_activation)
+        dr, tl = self._opt(direction, np.uint8), self._opt(ttl, np.int64)
+        fw, mf = self._opt(forward_count, np.uint8), self._opt(msg_flags, np.uint8)
+        fl, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        rc = self._opt(request_count, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        st = gd_turn_state(p(fl), p(nr), p(rc), hard_limit, hard_limit_sw, max_forward_count, int(chain))
+        ctx, rst = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        perm, offs = np.zeros(n, np.uint32), np.zeros(n_ctx + 3, np.uint32)
+        turn, nro, run = np.zeros(n, np.uint8), np.zeros(n_ctx, np.uint32), np.zeros(n_ctx, np.uint32)
+        start, n_start = np.zeros(max(n, 1), np.uint32), np.zeros(1, np.uint32)
+        wperm, woff = np.zeros(n, np.uint32), np.zeros(n_ctx + 2, np.uint32)
+        io, result, keep = self._activate_io_host(n, cap_new, ctx_base, new_ctx, new_placement, terminating)
+
+        def full():
+            return dict(result(), ctx=ctx, status=rst, perm=perm, offsets=offs, turn=turn, num_running_out=nro,
+                        running_idx=run, start_idx=start[:int(n_start[0])].copy(), wait_perm=wperm, wait_offsets=woff)
+        try:
+            self._c(lib.gd_receive_activate_turns(self.h, _ptr(tg), _ptr(ta), p(dr), n, n_ctx, None, _ptr(ctx),
+                                                  _ptr(rst), _ptr(perm), _ptr(offs), p(tl), p(fw), p(mf), p(sa),
+                                                  C.byref(st), _ptr(turn), _ptr(nro), _ptr(run), _ptr(start),
+                                                  _ptr(n_start), _ptr(wperm), _ptr(woff), C.byref(io)))
+        except GrainDispatchError as ex:
+            ex.arrays = full()
+            raise
+        return full()
+
+    def receive_activate_turns_device(self, d_tg: int, d_ta: int, d_dir: Optional[int], n: int, n_ctx: int, d_ctx: int,
+                                      d_status: int, d_perm: Optional[int], d_offsets: Optional[int],
+                                      d_ttl: Optional[int], d_forward_count: Optional[int], d_msg_flags: Optional[int],
+                                      d_sending_activation: Optional[int], state: gd_turn_state, d_turn: int,
+                                      d_num_running_out: int, d_running_idx: int, act: gd_activate_io,
+                                      d_start_idx: Optional[int] = None, d_n_start: Optional[int] = None,
+                                      d_wait_perm: Optional[int] = None, d_wait_offsets: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_receive_activate_turns_device(
+            self.h, V(d_tg), V(d_ta), V(d_dir), n, n_ctx, None, V(d_ctx), V(d_status), V(d_perm), V(d_offsets), V(d_ttl),
+            V(d_forward_count), V(d_msg_flags), V(d_sending_activation), C.byref(state), V(d_turn), V(d_num_running_out),
+            V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm), V(d_wait_offsets), C.byref(act)))
+
+    def receive_activate_turns_frames(self, buf: bytes, offsets, n_ctx: int, ctx_flags, num_running, request_count,
+                                      cap_new: int, ctx_base: int = 0, new_ctx=None, terminating: bool = False,
+                                      ttl_age_ticks: int = 0, msg_flags_or=None, hard_limit: int = 0,
+                                      hard_limit_sw: int = 0, max_forward_count: int = 2, chain: bool = False) -> dict:
+        """gd_receive_activate_turns_frames: receive_activate_turns()'s dict, fed from the receive buffer."""
+        b = np.frombuffer(buf, dtype=np.uint8) if len(buf) else np.zeros(1, dtype=np.uint8)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.uint64))
+        n = len(off)
+        mor = self._opt(msg_flags_or, np.uint8)
+        fl, nr = self._opt(ctx_flags, np.uint8), self._opt(num_running, np.uint32)
+        rc = self._opt(request_count, np.uint32)
+        p = lambda a: None if a is None else _ptr(a)
+        st = gd_turn_state(p(fl), p(nr), p(rc), hard_limit, hard_limit_sw, max_forward_count, int(chain))
+        ctx, rst = np.zeros(n, np.uint32), np.zeros(n, np.uint8)
+        perm, offs = np.zeros(n, np.uint32), np.zeros(n_ctx + 3, np.uint32)
+        turn, nro, run = np.zeros(n, np.uint8), np.zeros(n_ctx, np.uint32), np.zeros(n_ctx, np.uint32)
+        start, n_start = np.zeros(max(n, 1), np.uint32), np.zeros(1, np.uint32)
+        wperm, woff = np.zeros(n, np.uint32), np.zeros(n_ctx + 2, np.uint32)
+        io, result, keep = self._activate_io_host(n, cap_new, ctx_base, new_ctx, None, terminating)
+
+        def full():
+            return dict(result(), ctx=ctx, status=rst, perm=perm, offsets=offs, turn=turn, num_running_out=nro,
+                        running_idx=run, start_idx=start[:int(n_start[0])].copy(), wait_perm=wperm, wait_offsets=woff)
+        try:
+            self._c(lib.gd_receive_activate_turns_frames(
+                self.h, _ptr(b), len(buf), _ptr(off), n, n_ctx, None, None, None, _ptr(ctx), _ptr(rst), _ptr(perm),
+                _ptr(offs), ttl_age_ticks, p(mor), C.byref(st), _ptr(turn), _ptr(nro), _ptr(run), _ptr(start),
+                _ptr(n_start), _ptr(wperm), _ptr(woff), C.byref(io)))
+        except GrainDispatchError as ex:
+            ex.arrays = full()
+            raise
+        return full()
+
+    def receive_activate_turns_frames_device(self, d_buf: int, buf_len: int, d_offsets: int, n: int, n_ctx: int,
+                                             d_ctx: int, d_status: int, d_perm: Optional[int], d_offs: Optional[int],
+                                             ttl_age_ticks: int, d_msg_flags_or: Optional[int], state: gd_turn_state,
+                                             d_turn: int, d_num_running_out: int, d_running_idx: int,
+                                             act: gd_activate_io, d_start_idx: Optional[int] = None,
+                                             d_n_start: Optional[int] = None, d_wait_perm: Optional[int] = None,
+                                             d_wait_offsets: Optional[int] = None):
+        V = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_receive_activate_turns_frames_device(
+            self.h, V(d_buf), buf_len, V(d_offsets), n, n_ctx, None, None, None, V(d_ctx), V(d_status), V(d_perm),
+            V(d_offs), ttl_age_ticks, V(d_msg_flags_or), C.byref(state), V(d_turn), V(d_num_running_out),
+            V(d_running_idx), V(d_start_idx), V(d_n_start), V(d_wait_perm), V(d_wait_offsets), C.byref(act)))
 
     # -- per-kernel timing ----------------------------------------------------------
     def kernel_times(self) -> dict:
