@@ -469,6 +469,17 @@ int      gd_microbatch_run(gd_microbatch* mb, uint32_t n, int use_graph);
                                          TargetObserver -> all but TargetSilo decoded. C# decodes it */
 #define GD_FRAME_MALFORMED      0x08u /* lengths run past the header or the buffer: nothing decoded  */
 #define GD_FRAME_TARGET_KEYEXT  0x10u /* TargetGrain carries a KeyExt string (not returned)          */
+#define GD_FRAME_INVALIDATION   0x20u /* GD_OPT_WALK_INVALIDATION 1 only: the mask has the
+                                         CacheInvalidationHeader bit (any count, zero included).  The
+                                         field -- int32 count, then per entry a 24-B SiloAddress and two
+                                         UniqueKeys with their KeyExt strings -- was stepped over: every
+                                         other output, the mask included, is that of the same frame with
+                                         the field cut out (a KeyExt offset stays absolute in buf).  A
+                                         negative count or entries that run past the header:
+                                         GD_FRAME_MALFORMED alone.  RequestContext, and TargetObserver
+                                         ahead of TargetSilo, stay GD_FRAME_FALLBACK.  With the option at
+                                         0 (default) the flag is never set and such a frame is
+                                         GD_FRAME_FALLBACK.  gd_sniff_frames* reads the entries          */
 
 #define GD_ROUTE_ADDRESSED      5 /* frame address already complete: not looked up (Dispatcher.cs:718) */
 #define GD_ROUTE_UNDECODED      6 /* no TargetGrain decoded (absent / fallback / malformed): C# path    */
@@ -2029,6 +2040,13 @@ int gd_set_kernel_timing(gd_handle* h, int enable);   /* 0 off, 1 every launch, 
                                    of its memory traffic alone (k_fan_bound: the same expansion reads, one
                                    64-B index group read a message and the same result writes into scratch,
                                    no ring search, no walk), timed under its own name: 0 (default) / 1 */
+#define GD_OPT_WALK_INVALIDATION 18 /* frames that carry a CacheInvalidationHeader (every request
+                                   gd_forward_frames* forwards, and the answers to them): 0 (default) they go
+                                   back to C# -- GD_FRAME_FALLBACK, GD_ENC_FALLBACK, GD_RSPST_FALLBACK; 1 the
+                                   decoder (every gd_*_frames* call it feeds, gd_receive_activate_turns_frames*'
+                                   IsNewPlacement walk included), gd_encode_frames* and gd_respond_frames* step
+                                   over the field (GD_FRAME_INVALIDATION, and the two stages' contracts).  With 0
+                                   the kernels launched are the ones without the walk, bit for bit */
 int gd_option_set(gd_handle* h, int option, int64_t value);
 int gd_option_get(const gd_handle* h, int option, int64_t* value);
 
@@ -2121,7 +2139,9 @@ int gd_route_bound_device(gd_handle* h, const gd_key* d_keys, uint32_t n, uint32
  *   the decoder's GD_FRAME_MALFORMED length conditions          -> GD_ENC_MALFORMED
  *   GD_ROUTE_ADDRESSED (complete address, Dispatcher.cs:718)    -> GD_ENC_COPIED, a byte-for-byte copy
  *   CacheInvalidationHeader or RequestContext present, or TargetObserver and TransactionInfo both present (an
- *     insertion point lies behind an object-serialized field)   -> GD_ENC_FALLBACK, C# serializes it
+ *     insertion point lies behind an object-serialized field)   -> GD_ENC_FALLBACK, C# serializes it.  With
+ *     GD_OPT_WALK_INVALIDATION 1 a CacheInvalidationHeader alone does not: the field is stepped over (a
+ *     negative count or entries past the header: GD_ENC_MALFORMED) and copied through in front of Category
  *   the header walk runs off the header                          -> GD_ENC_MALFORMED
  *   silo[i] >= n_silos                                           -> GD_ENC_NO_SILO
  *   act[i] has no ActivationId (index past the map, or all zero) -> GD_ENC_NO_ID
@@ -2201,6 +2221,14 @@ int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const u
  *   the decoder's GD_FRAME_MALFORMED length conditions           -> GD_RSPST_MALFORMED
  *   CacheInvalidationHeader present (object-serialized ahead of Direction, which cannot then be read)
  *                                                                -> GD_RSPST_FALLBACK
+ *     With GD_OPT_WALK_INVALIDATION 1 the field is stepped over instead (a negative count or entries past the
+ *     header: the next line's GD_RSPST_MALFORMED).  CreateResponseMessage copies the header
+ *     (MessageFactory.cs:90): with count > 0 the answer carries the request's count and entries, byte for byte,
+ *     in front of Category; with count 0 the answer's mask drops the bit (the Deserializer builds no list then,
+ *     Message.cs:1254-1265).  One such frame stays GD_RSPST_FALLBACK, decided last, where it would have been
+ *     GD_RSPST_OK: count > 0, a Category byte present with the enum's default value (the answer drops it) and a
+ *     non-empty DebugContext behind it (kept) -- the entries and DebugContext would be two runs of the request,
+ *     and the plan record has no run left.  The reference's serializer never writes a default-valued Category
  *   the walk to Direction runs off the header                    -> GD_RSPST_MALFORMED
  *   the request's Direction byte present and != 0 (RejectMessage :209-221; a frame without Direction counts as a
  *     request)                                                   -> GD_RSPST_DISCARDED

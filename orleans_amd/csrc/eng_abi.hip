@@ -849,6 +849,10 @@ int gd_option_set(gd_handle* h, int option, int64_t v) {
             if (!in(0, 1)) break;
             h->fan_bound = v != 0;
             return GD_OK;
+        case GD_OPT_WALK_INVALIDATION:
+            if (!in(0, 1)) break;
+            h->walk_cih = v != 0;
+            return GD_OK;
         default: return set_err(h, GD_EINVAL, "gd_option_set: unknown option %d", option);
     }
     return set_err(h, GD_EINVAL, "gd_option_set: option %d: value %lld out of range", option, (long long)v);
@@ -875,6 +879,7 @@ int gd_option_get(const gd_handle* hc, int option, int64_t* v) {
         case GD_OPT_B2_ORDER: *v = h->b2_order; return GD_OK;
         case GD_OPT_MB_POLL: *v = h->mb_poll ? 1 : 0; return GD_OK;
         case GD_OPT_FAN_BOUND: *v = h->fan_bound ? 1 : 0; return GD_OK;
+        case GD_OPT_WALK_INVALIDATION: *v = h->walk_cih ? 1 : 0; return GD_OK;
         default: return set_err(h, GD_EINVAL, "gd_option_get: unknown option %d", option);
     }
 }

@@ -131,7 +131,12 @@ int frame_new_placement_device(gd_handle* h, const uint8_t* buf, uint64_t len, c
     if (n == 0) return GD_OK;
     GD_TRY(ensure(h, h->actv_scr[9], (size_t)n + 16));
     uint8_t* newp = (uint8_t*)h->actv_scr[9].p;
-    GD_TRY(launch(h, "k_actv_newp", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_actv_newp, buf, len, off, st, n, newp));
+    if (h->walk_cih)                    // GD_OPT_WALK_INVALIDATION
+        GD_TRY(launch(h, "k_actv_newp_cih", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_actv_newp<true>, buf, len, off,
+                      st, n, newp));
+    else
+        GD_TRY(launch(h, "k_actv_newp", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_actv_newp<false>, buf, len, off,
+                      st, n, newp));
     *out = newp;
     return GD_OK;
 }

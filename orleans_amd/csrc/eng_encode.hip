@@ -45,8 +45,12 @@ int encode_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint
     uint32_t* lens = (uint32_t*)h->enc_scr[1].p;
     uint32_t* offs = (uint32_t*)h->enc_scr[2].p;
     const EncTab t = enc_tab(h);
-    GD_TRY(launch(h, "k_enc_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_enc_plan, buf, buf_len, frame_off, n,
-                  silo, act, status, placed, new_type, t, plan, lens, enc_status));
+    if (h->walk_cih)                    // GD_OPT_WALK_INVALIDATION
+        GD_TRY(launch(h, "k_enc_plan_cih", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_enc_plan<true>, buf, buf_len,
+                      frame_off, n, silo, act, status, placed, new_type, t, plan, lens, enc_status));
+    else
+        GD_TRY(launch(h, "k_enc_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_enc_plan<false>, buf, buf_len,
+                      frame_off, n, silo, act, status, placed, new_type, t, plan, lens, enc_status));
     GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
                   (const uint32_t*)lens, order, n, offs));
     GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "encode"));

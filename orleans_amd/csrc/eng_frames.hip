@@ -48,6 +48,12 @@ int decode_frames_device(gd_handle* h, const uint8_t* buf, uint64_t len, const u
         ff.tg_ext_len = (int32_t*)h->fr_ext[1].p;
     }
     // the turn headers come out of the same walk; without them the kernel every other caller launches
+    const dim3 g(blocks_for(n, BLOCK)), b(BLOCK);
+    if (h->walk_cih) {                  // GD_OPT_WALK_INVALIDATION: the instantiations that step over the field
+        if (want_turn)
+            return launch(h, "k_decode_frames_turn_cih", g, b, 0, k_decode_frames<true, true>, buf, len, off, n, ff, tf);
+        return launch(h, "k_decode_frames_cih", g, b, 0, k_decode_frames<false, true>, buf, len, off, n, ff, tf);
+    }
     if (want_turn)
         return launch(h, "k_decode_frames_turn", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_decode_frames<true>, buf,
                       len, off, n, ff, tf);

@@ -42,8 +42,12 @@ int respond_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uin
     uint32_t* offs = (uint32_t*)h->rsp_scr[2].p;
     if (!body || !body_off) body = nullptr, body_off = nullptr;
     const RspIn in{kind, result, rejection_type, info, body_off, (const uint32_t*)h->rsp_tab[1].p, h->rsp_ninfo};
-    GD_TRY(launch(h, "k_rsp_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_rsp_plan, buf, buf_len, frame_off, n,
-                  in, plan, lens, rsp_status));
+    if (h->walk_cih)                    // GD_OPT_WALK_INVALIDATION
+        GD_TRY(launch(h, "k_rsp_plan_cih", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_rsp_plan<true>, buf, buf_len,
+                      frame_off, n, in, plan, lens, rsp_status));
+    else
+        GD_TRY(launch(h, "k_rsp_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_rsp_plan<false>, buf, buf_len,
+                      frame_off, n, in, plan, lens, rsp_status));
     GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
                   (const uint32_t*)lens, order, n, offs));
     GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "respond"));

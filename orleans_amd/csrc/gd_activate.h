@@ -335,7 +335,9 @@ static __global__ void __launch_bounds__(BLOCK) k_actv_clear(const ActvWords* __
 // Message.IsNewPlacement of the GD_RECV_NULL_CONTEXT frames (the decoder steps over the token): the header walk
 // in the serializer's order (Message.cs:1247-1356) up to the bool tokens, through global memory (lim = 0: these
 // frames are few).  True iff mask bit 18 is set and the token is SerializationTokenType.True.  A NULL_CONTEXT
-// frame decoded completely, so its mask has neither CacheInvalidationHeader nor RequestContext.
+// frame decoded completely, so its mask has neither CacheInvalidationHeader nor RequestContext -- or, with WALK
+// (GD_OPT_WALK_INVALIDATION), a CacheInvalidationHeader the decoder stepped over, which this walk steps over too.
+template <bool WALK = false>
 static __global__ void __launch_bounds__(BLOCK) k_actv_newp(const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                      const uint64_t* __restrict__ frame_off,
                                                      const uint8_t* __restrict__ rs, uint32_t n,
@@ -355,10 +357,11 @@ static __global__ void __launch_bounds__(BLOCK) k_actv_newp(const uint8_t* __res
             const int32_t hl = (int32_t)hw.c.u32(0), bl = (int32_t)hw.c.u32(4);
             const uint32_t m = hw.c.u32(8);
             const bool ok = !(hl < 4 || bl < 0 || (uint64_t)hl + (uint64_t)bl > buf_len - start - 8) &&
-                            !(m & (H_CACHE_INVALIDATION | H_REQUEST_CONTEXT));
+                            !(m & ((WALK ? 0u : H_CACHE_INVALIDATION) | H_REQUEST_CONTEXT));
             if (ok && (m & H_IS_NEW_PLACEMENT)) {
                 hw.p = 12;
                 hw.end = 8u + (uint32_t)hl;
+                if (WALK && (m & H_CACHE_INVALIDATION)) hw.skip_invalidation();
                 if (m & H_CATEGORY) hw.take(1);
                 if (m & H_DEBUG_CONTEXT) hw.skip_string();
                 if ((m & H_DIRECTION) && !hw.bad) hw.take(1);

@@ -107,6 +107,9 @@ __device__ __forceinline__ EncMap enc_map(const EncPlan& p) {
 }
 
 // ------------------------------------------------------------------ k_enc_plan
+// WALK (GD_OPT_WALK_INVALIDATION): a CacheInvalidationHeader is stepped over, so the four positions lie behind
+// it and k_enc_write copies it through in front of Category; without it such a frame is ENC_FALLBACK.
+template <bool WALK = false>
 static __global__ __launch_bounds__(BLOCK) void k_enc_plan(const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                     const uint64_t* __restrict__ frame_off, uint32_t n,
                                                     const uint32_t* __restrict__ silo,
@@ -184,11 +187,12 @@ static __global__ __launch_bounds__(BLOCK) void k_enc_plan(const uint8_t* __rest
             hw.p = 12;
             hw.end = 8u + (uint32_t)hl;
             const uint32_t m = hw.c.u32(8);
-            if ((m & (H_CACHE_INVALIDATION | H_REQUEST_CONTEXT)) ||
+            if ((m & ((WALK ? 0u : H_CACHE_INVALIDATION) | H_REQUEST_CONTEXT)) ||
                 ((m & H_TARGET_OBSERVER) && (m & H_TRANSACTION_INFO))) {
                 st = ENC_FALLBACK;
             } else {
                 // HeadersContainer.Serializer order (Message.cs:1126-1245)
+                if (WALK && (m & H_CACHE_INVALIDATION)) hw.skip_invalidation();
                 if (m & H_CATEGORY) hw.take(1);
                 if (m & H_DEBUG_CONTEXT) hw.skip_string();
                 if ((m & H_DIRECTION) && !hw.bad) hw.take(1);

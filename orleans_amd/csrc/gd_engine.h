@@ -317,6 +317,7 @@ struct gd_handle {
     bool fan_bound = false;     // a k_fan_bound launch beside each 8-B-index k_fan_route (GD_OPT_FAN_BOUND)
     uint32_t fan_bound_n = 0;   // ... before it on even launches, after it on odd ones
     bool mb_poll = true;        // micro-batches: completion by the sort's pinned count (GD_OPT_MB_POLL)
+    bool walk_cih = false;      // the frame stages step over a CacheInvalidationHeader (GD_OPT_WALK_INVALIDATION)
     int tune_pin[GD_TUNE_KINDS] = {-1, -1, -1, -1, -1};   // gd_tune_set: pinned variant per kind, -1 measured
     int msd_mode = 1;           // two-level bucketing (gd_msd.h, gd_msd2.h): 0 off, 1 measured (default), 2 always (GD_MSD)
     uint32_t l2_small = 1024;   // three-pass form: ranges of at most this many messages are sorted one wave a range

@@ -38,7 +38,8 @@ enum : uint32_t {
 };
 
 // frame flags (GD_FRAME_* in include/graindispatch.h)
-enum : uint32_t { FR_HAS_TARGET = 1u, FR_COMPLETE = 2u, FR_FALLBACK = 4u, FR_MALFORMED = 8u, FR_TARGET_KEYEXT = 16u };
+enum : uint32_t { FR_HAS_TARGET = 1u, FR_COMPLETE = 2u, FR_FALLBACK = 4u, FR_MALFORMED = 8u, FR_TARGET_KEYEXT = 16u,
+                  FR_INVALIDATION = 32u };
 
 // route statuses added for frames (GD_ROUTE_ADDRESSED / GD_ROUTE_UNDECODED)
 constexpr uint8_t ROUTE_ADDRESSED = 5, ROUTE_UNDECODED = 6;
@@ -140,6 +141,24 @@ struct HeaderWalk {
         if (ext_len) *ext_len = e;
         return k;
     }
+    // The CacheInvalidationHeader field (GD_OPT_WALK_INVALIDATION; p stands at its first byte): int32 count, then
+    // count x (24-B SiloAddress, GrainId, ActivationId), as k_fwd_plan (gd_forward.h) and k_sniff_count
+    // (gd_sniff.h) walk it.  A negative count sets bad; an entry holds >= 80 B, so the header bounds the loop.
+    // Returns the count.
+    __device__ __forceinline__ uint32_t skip_invalidation() {
+        if (bad || !take(4)) return 0;
+        const int32_t cnt = (int32_t)c.u32(p - 4);
+        if (cnt < 0) {
+            bad = true;
+            return 0;
+        }
+        for (uint32_t k = 0; k < (uint32_t)cnt && !bad; ++k) {
+            if (!take(24)) break;
+            key(nullptr);
+            key(nullptr);
+        }
+        return (uint32_t)cnt;
+    }
 };
 
 __device__ __forceinline__ void store_key(uint64_t* out, uint32_t i, const Key3& k) {
@@ -156,8 +175,10 @@ __device__ __forceinline__ void store_silo(uint32_t* out, uint32_t i, const uint
 }
 
 // TURN: the turn-admission headers (FrameTurnFields t) come out of the same walk; without it the walk steps
-// over their bytes and t is never read.
-template <bool TURN>
+// over their bytes and t is never read.  WALK (GD_OPT_WALK_INVALIDATION): a CacheInvalidationHeader is stepped
+// over and flagged FR_INVALIDATION, every other output being that of the frame with the field cut out; without
+// it such a frame is FR_FALLBACK.
+template <bool TURN, bool WALK = false>
 static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                          const uint64_t* __restrict__ frame_off, uint32_t n,
                                                          FrameFields o, FrameTurnFields t) {
@@ -239,9 +260,14 @@ static __global__ __launch_bounds__(BLOCK) void k_decode_frames(const uint8_t* _
         const uint32_t m = mask;
         const uint32_t full = H_TARGET_ACTIVATION | H_TARGET_SILO | H_TARGET_GRAIN;
         if ((m & full) == full) flags |= FR_COMPLETE;
-        if (m & (H_CACHE_INVALIDATION | H_REQUEST_CONTEXT)) {
+        if (WALK && (m & H_CACHE_INVALIDATION)) {
+            flags |= FR_INVALIDATION;
+            mask &= ~H_CACHE_INVALIDATION;     // every output but this flag: the frame without the field
+        }
+        if (m & ((WALK ? 0u : H_CACHE_INVALIDATION) | H_REQUEST_CONTEXT)) {
             flags |= FR_FALLBACK;          // object-serialized field before TargetGrain: nothing decoded
         } else {
+            if (WALK && (m & H_CACHE_INVALIDATION)) hw.skip_invalidation();
             if ((m & H_CATEGORY) && hw.take(1)) cat = hw.c.u8(hw.p - 1);
             if (m & H_DEBUG_CONTEXT) hw.skip_string();
             if ((m & H_DIRECTION) && !hw.bad && hw.take(1)) dir = hw.c.u8(hw.p - 1);

@@ -135,6 +135,13 @@ struct RspIn {
     uint32_t n_info;
 };
 
+// WALK (GD_OPT_WALK_INVALIDATION): a CacheInvalidationHeader is stepped over.  CreateResponseMessage copies the
+// header (MessageFactory.cs:90) and the field stands directly in front of Category in the request and in the
+// answer, so its bytes [12, p0) join run 0 when it has entries; with none the answer drops the bit, as the
+// Deserializer builds no list then (Message.cs:1254-1265).  Run 0 has to stay one run: a frame with entries, a
+// Category byte of the enum's default (dropped) and a DebugContext behind it (kept) is RSPST_FALLBACK where it
+// would have been RSPST_OK.  Without WALK every frame with the field is RSPST_FALLBACK.
+template <bool WALK = false>
 static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __restrict__ buf, uint64_t buf_len,
                                                     const uint64_t* __restrict__ frame_off, uint32_t n, RspIn in,
                                                     RspPlan* __restrict__ plan, uint32_t* __restrict__ out_len,
@@ -178,6 +185,7 @@ static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __rest
     for (uint32_t k = 0; k < RSP_RUNS; ++k) pos[k] = len[k] = 0;
     uint32_t st = RSPST_SKIPPED, olen = 0, om = 0, flags = 0, info_pos = 0, info_len = 0, rt = 0, res = 0, hl_out = 0,
              bl_out = 0;
+    bool split0 = false;                             // WALK only: run 0 would be two runs
     const uint32_t kind = in.kind[i];
     if (kind == RSP_RESPONSE || kind == RSP_REJECTION) {
         const uint64_t a0 = start & ~3ull;
@@ -207,10 +215,11 @@ static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __rest
             hw.end = 8u + (uint32_t)hl;
             const uint32_t m = hw.c.u32(8);
             st = RSPST_OK;
-            if (m & H_CACHE_INVALIDATION) {
+            if (!WALK && (m & H_CACHE_INVALIDATION)) {
                 st = RSPST_FALLBACK;                 // object-serialized ahead of Direction: nothing can be read
             } else {
                 // HeadersContainer.Serializer order (Message.cs:1126-1244)
+                const bool cih = WALK && (m & H_CACHE_INVALIDATION) && hw.skip_invalidation() > 0;
                 const uint32_t p0 = hw.p;
                 uint32_t cat = 0;
                 if ((m & H_CATEGORY) && hw.take(1)) cat = hw.c.u8(hw.p - 1);
@@ -232,6 +241,12 @@ static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __rest
                     const uint32_t b1 = (dbg > 0) ? e_dbg : p_dbg;
                     pos[0] = b0;
                     len[0] = b1 > b0 ? b1 - b0 : 0u;
+                    if (WALK && cih) {               // ... and the entries stand in front of them
+                        split0 = p_dbg != p0 && cat == 0 && dbg > 0;     // a dropped byte between the two
+                        pos[0] = 12;
+                        len[0] = ((cat != 0 || dbg > 0) ? b1 : p0) - 12;
+                        om |= H_CACHE_INVALIDATION;
+                    }
                     if (cat != 0) om |= H_CATEGORY;
                     if (dbg > 0) om |= H_DEBUG_CONTEXT;
                     if ((m & H_TIME_TO_LIVE) && hw.take(8)) {
@@ -367,6 +382,7 @@ static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __rest
             }
         }
     }
+    if (WALK && split0 && st == RSPST_OK) st = RSPST_FALLBACK;
     if (st == RSPST_OK) {
         uint4* pp = reinterpret_cast<uint4*>(plan + i);
         pp[0] = make_uint4(pos[0], pos[1], pos[2], pos[3]);

@@ -22,6 +22,7 @@ RING_DIRECTORY, RING_CONSISTENT, RING_VIRTUAL_BUCKETS = 0, 1, 2
 ROUTE_OK, ROUTE_MISS, ROUTE_SYSTEM_TARGET, ROUTE_MEMBERSHIP, ROUTE_KEYEXT = 0, 1, 2, 3, 4
 ROUTE_ADDRESSED, ROUTE_UNDECODED = 5, 6
 FRAME_HAS_TARGET, FRAME_COMPLETE, FRAME_FALLBACK, FRAME_MALFORMED, FRAME_TARGET_KEYEXT = 1, 2, 4, 8, 16
+FRAME_INVALIDATION = 32       # GD_OPT_WALK_INVALIDATION 1: the frame's CacheInvalidationHeader was stepped over
 NO_ACTIVATION = 0xFFFFFFFF
 NO_SILO = 0xFFFFFFFF
 NO_SILO16 = 0xFFFF            # GD_NO_SILO16: the compact routes' packed GD_NO_SILO
@@ -741,6 +742,9 @@ OPTIONS = {"probe": 1, "bucket": 2, "l2_small": 3, "stable_rank": 4, "wire_heade
            "idx16": 7, "host_chunk": 8, "mb_zerocopy": 9, "mb_split": 10, "mb_trace": 11, "l2_staged": 12,
            "l2_mid": 13, "b2_persist": 14, "b2_order": 15, "mb_poll": 16,
            "fan_bound": 17}
+# GD_OPT_WALK_INVALIDATION: set_option / get_option take it by number (OPTIONS names the options whose defaults
+# the configuration tests enumerate)
+OPT_WALK_INVALIDATION = 18
 TUNE_KINDS = {"probe_keys": 0, "probe_n1": 1, "probe_fanout": 2, "probe_nodes": 3, "bucket": 4}
 # Options applied to every handle this process creates, before its own `options=` (the test and tool
 # harness sets these; a C# host calls gd_option_set on its handle instead).
