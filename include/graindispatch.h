@@ -2449,9 +2449,9 @@ int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uin
  *     TransactionInfo are both present)                             -> GD_FWDST_MALFORMED
  *   RequestContext present; TargetObserver and TransactionInfo both present; TargetGrain absent; TargetGrain a
  *     system target (SendSystemTargetMessage, :606-609)             -> GD_FWDST_FALLBACK, C# forwards it
- *   ForwardCount >= max_forward_count (MayForward, :627-630)        -> GD_FWDST_REJECT: no bytes; the reference's
- *     rejection carries the extended invalidation header (MessageFactory.cs:90), which gd_respond_frames does not
- *     write: C# rejects it
+ *   ForwardCount >= max_forward_count (MayForward, :627-630)        -> GD_FWDST_REJECT: no bytes here; the
+ *     reference's rejection carries the extended invalidation header (MessageFactory.cs:90), which
+ *     gd_respond_frames does not write: gd_forward_reject_frames* (below) writes it from this same batch
  *   old_act[i] names an activation and local_silo >= n_silos        -> GD_FWDST_NO_SILO
  *   old_act[i] names an activation without an ActivationId          -> GD_FWDST_NO_ID
  *   the address written (the forwarding address, else the route's): its silo >= n_silos -> GD_FWDST_NO_SILO,
@@ -2476,8 +2476,8 @@ int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uin
  * [out_off[offsets[q]], out_off[offsets[q + 1]]).  It returns the outputs of all three stages (d_queue may be
  * NULL; target is required); GD_ESTATE before gd_send_configure too.  Misses leave unaddressed: gd_route_place* on
  * the returned keys is the caller's next step.
- * Left to C#: the rejections of messages that may not forward, the cross-cluster return, system targets and
- * FALLBACK frames.  InvalidateCacheEntry -- on the receiving side, and the sending side's own call for the old
+ * Left to C#: the cross-cluster return, system targets and FALLBACK frames.  The rejections of messages that may
+ * not forward are gd_forward_reject_frames*' (below).  InvalidateCacheEntry -- on the receiving side, and the sending side's own call for the old
  * address (Dispatcher.cs:478, :497) -- is the sniff stage's (gd_sniff_invalidate*, gd_cache_invalidate*, below). */
 #define GD_FWD_NONE    0
 #define GD_FWD_FORWARD 1
@@ -2520,6 +2520,81 @@ int gd_forward_send(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uin
                     uint8_t* out_status, uint8_t* out_send_status, uint32_t* out_queue, uint32_t* out_perm,
                     uint32_t* out_offsets, uint8_t* out_buf, uint64_t out_cap, uint64_t* out_off, uint8_t* fwd_status,
                     gd_key* target, uint64_t* out_total);
+
+/* ---- forward rejections: TryForwardRequest's failure arm + RejectMessage + Serialize for a batch ---
+ * A request that must be forwarded but has been forwarded MaxForwardCount times already is rejected:
+ * Dispatcher.TryForwardRequest (Dispatcher.cs:526-570) appends the old address to the message's
+ * CacheInvalidationHeader -- ahead of MayForward --, TryForwardMessage (:591-599, :627-630) returns false without
+ * counting ForwardCount up, RejectMessage(message, Transient, exc, str) (:203-222) answers a Request with
+ * MessageFactory.CreateRejectionResponse (MessageFactory.cs:49-111) and drops any other direction, and
+ * CreateResponseMessage copies the request's CacheInvalidationHeader (:90): the rejection carries the old entries
+ * plus the one just appended.  These are the frames gd_forward_frames* marks GD_FWDST_REJECT; this stage takes the
+ * same source frames and the same gd_forward_batch and writes their answers, output frame j being input frame
+ * order[j].
+ *   batch->buf, buf_len, frame_off, kind, old_act, max_forward_count, local_silo: gd_forward_frames*' meaning.
+ *     fwd_silo and fwd_act are ignored.
+ *   info[i]: an index into gd_respond_configure's strings, as gd_respond_frames' info; GD_RSP_NO_INFO or any index
+ *     >= n_info: no RejectionInfo.  (The reference's string holds Message.ToString(): the caller's choice.)
+ *   body, body_off: gd_respond_frames' pair (n + 1 non-decreasing entries); the serialized exc, or null, is the
+ *     caller's.
+ * The invalidation field is always walked, as in the forward writer, whatever GD_OPT_WALK_INVALIDATION is set to.
+ * The answer's header, in HeadersContainer.Serializer order (Message.cs:1126-1244):
+ *   CacheInvalidationHeader  when old_act[i] names an activation: count = old count + 1 (1 when the field was
+ *                     absent), the old entries as they stand, then one entry exactly as the forward writer writes
+ *                     it: silos[local_silo] (24 B), the frame's TargetGrain UniqueKey with its KeyExt bytes as they
+ *                     stand, the ActivationId of old_act[i] with a null KeyExt (28 B); the mask has bit 1.
+ *                     When old_act[i] == GD_NO_ACTIVATION, or old_act is NULL: a request's field with count > 0 is
+ *                     copied byte for byte, one with count 0 is dropped, bit included, an absent one stays absent.
+ *   everything behind it     what gd_respond_frames* writes for kind GD_RSP_REJECTION with rejection type 0
+ *                     (Transient): Category dropped when its byte is 0, DebugContext dropped when empty, Direction
+ *                     1, TimeToLive, CorrelationId and the two True tokens carried over, RejectionInfo by info[i],
+ *                     no RejectionType byte, Result 2, Target* and Sending* exchanged, TransactionInfo kept,
+ *                     ForwardCount and the rest of that contract's "dropped" list dropped.  headerLength is
+ *                     recomputed; bodyLength is the supplied body's length.
+ * The stage has no fallback of its own: the frame gd_respond_frames* keeps GD_RSPST_FALLBACK under the walk option
+ * (entries, a default-valued Category byte, a non-empty DebugContext) is GD_FWDREJ_OK here.
+ * Status, one byte per input frame, decided in this order:
+ *   kind not GD_FWD_FORWARD                                          -> GD_FWDREJ_SKIPPED
+ *   the forward writer's GD_FWDST_MALFORMED conditions               -> GD_FWDREJ_MALFORMED
+ *   the forward writer's GD_FWDST_FALLBACK conditions (RequestContext present; TargetObserver and TransactionInfo
+ *     both present; TargetGrain absent; a system target: they cover every FALLBACK of gd_respond_frames)
+ *                                                                    -> GD_FWDREJ_FALLBACK
+ *   ForwardCount < max_forward_count (absent counts as 0)            -> GD_FWDREJ_MAY_FORWARD: the forward writer's
+ *   the Direction byte present and != 0 (Dispatcher.cs:209-221)      -> GD_FWDREJ_DISCARDED
+ *   old_act[i] names an activation and local_silo >= n_silos         -> GD_FWDREJ_NO_SILO
+ *   old_act[i] names an activation without an ActivationId           -> GD_FWDREJ_NO_ID
+ *   else                                                             -> GD_FWDREJ_OK
+ * Only OK frames contribute bytes.  On any batch the frames marked DISCARDED, NO_SILO, NO_ID or OK are exactly the
+ * frames gd_forward_frames* marks GD_FWDST_REJECT, and the SKIPPED, MALFORMED and FALLBACK sets are the forward
+ * writer's.  order, out_off[n + 1], out_cap, GD_EFULL (nothing written, out_off still complete, the handle's
+ * device error word) and n == 0 are gd_encode_frames*'s.  Totals are 32-bit: the copied bytes are at most buf_len,
+ * and a frame gains at most the count (4), one entry (80 + its TargetGrain KeyExt bytes, which lie in buf: buf_len
+ * bounds their sum), Direction (1), the RejectionInfo length (4), Result (1) and the info string: 90 + the string.
+ * A call whose bound
+ *   2 * buf_len + body bytes + n * (90 + longest info string)
+ * reaches 2^32 is refused with GD_EINVAL; the device form cannot see the body bytes, checks the rest and leaves
+ * body_off[n] to the caller.  d_info, d_body / d_body_off (a pair) and d_order may each be NULL: no info, empty
+ * bodies, batch order.  Frames must be disjoint ranges of buf.  GD_ESTATE before gd_encode_configure or
+ * gd_respond_configure, and inside a hipGraph capture.
+ * The answers leave as gd_respond_frames*' do: gd_silo_index* on the decoder's sending_silo, gd_send_queues*, and
+ * its perm as `order` here.  ProcessRequestsToInvalidActivation(rejectMessages: true) needs nothing of this: it
+ * appends no entry and is gd_respond_frames* with kind GD_RSP_REJECTION under GD_OPT_WALK_INVALIDATION. */
+#define GD_FWDREJ_OK          0
+#define GD_FWDREJ_SKIPPED     1
+#define GD_FWDREJ_MALFORMED   2
+#define GD_FWDREJ_FALLBACK    3
+#define GD_FWDREJ_MAY_FORWARD 4
+#define GD_FWDREJ_DISCARDED   5
+#define GD_FWDREJ_NO_SILO     6
+#define GD_FWDREJ_NO_ID       7
+/* Device pointers (the batch struct is a host struct), enqueue only, no host read-back. */
+int gd_forward_reject_frames_device(gd_handle* h, const gd_forward_batch* batch, uint32_t n, const uint32_t* d_info,
+                                    const uint8_t* d_body, const uint64_t* d_body_off, const uint32_t* d_order,
+                                    uint8_t* d_out_buf, uint64_t out_cap, uint64_t* d_out_off, uint8_t* d_rej_status);
+/* Host pointers, synchronous; *out_total (may be NULL) = out_off[n]. */
+int gd_forward_reject_frames(gd_handle* h, const gd_forward_batch* batch, uint32_t n, const uint32_t* info,
+                             const uint8_t* body, const uint64_t* body_off, const uint32_t* order, uint8_t* out_buf,
+                             uint64_t out_cap, uint64_t* out_off, uint8_t* rej_status, uint64_t* out_total);
 
 /* ---- sniff stage: SniffIncomingMessage + InvalidateCacheEntry for a batch --------------------------
  * InsideRuntimeClient.SniffIncomingMessage (InsideRuntimeClient.cs:253-263) runs for every incoming message ahead of

@@ -130,6 +130,7 @@ void gd_destroy(gd_handle* h) {
     for (DevBuf& b : h->req_tab) free_buf(b);
     for (DevBuf& b : h->req_scr) free_buf(b);
     for (DevBuf& b : h->fwd_scr) free_buf(b);
+    for (DevBuf& b : h->rej_scr) free_buf(b);
     for (DevBuf& b : h->inv_scr) free_buf(b);
     for (DevBuf& b : h->col_scr) free_buf(b);
     for (DevBuf& b : h->stage_buf) free_buf(b);

@@ -200,6 +200,7 @@ struct gd_handle {
 
     // forward writer (gd_forward.h, eng_forward.hip): the ActivationIds, silos and type names are the encoder's
     DevBuf fwd_scr[5];                // plan records, output lengths, scanned offsets, the send stage's ttl and category
+    DevBuf rej_scr[3];                // forward rejections: plan records, output lengths, scanned offsets
 
     // sniff stage (gd_sniff.h, eng_sniff.hip): InvalidateCacheEntry's first-matching-entry word a cache slot (NONE32
     // between calls), the entries' slots, their classes

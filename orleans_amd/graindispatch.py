@@ -121,6 +121,7 @@ EXPORTED_SYMBOLS = [
     "gd_request_send",
     "gd_forward_kinds_device", "gd_forward_kinds", "gd_forward_frames_device", "gd_forward_frames",
     "gd_forward_send_device", "gd_forward_send",
+    "gd_forward_reject_frames_device", "gd_forward_reject_frames",
     "gd_sniff_frames_device", "gd_sniff_frames", "gd_cache_invalidate_device", "gd_cache_invalidate",
     "gd_sniff_invalidate_device", "gd_sniff_invalidate",
     "gd_activate_device", "gd_activate", "gd_receive_activate_turns_device", "gd_receive_activate_turns",
@@ -314,6 +315,8 @@ class gd_forward_batch(C.Structure):
 GD_FWD_NONE, GD_FWD_FORWARD = 0, 1
 (GD_FWDST_OK_ADDRESSED, GD_FWDST_OK_UNADDRESSED, GD_FWDST_SKIPPED, GD_FWDST_MALFORMED, GD_FWDST_FALLBACK,
  GD_FWDST_REJECT, GD_FWDST_NO_SILO, GD_FWDST_NO_ID) = range(8)
+(GD_FWDREJ_OK, GD_FWDREJ_SKIPPED, GD_FWDREJ_MALFORMED, GD_FWDREJ_FALLBACK, GD_FWDREJ_MAY_FORWARD,
+ GD_FWDREJ_DISCARDED, GD_FWDREJ_NO_SILO, GD_FWDREJ_NO_ID) = range(8)
 
 
 
@@ -528,6 +531,9 @@ def _load() -> C.CDLL:
         "gd_forward_frames_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P]),
         "gd_forward_frames": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, P, P, U64, P, P, P,
                                         C.POINTER(U64)]),
+        "gd_forward_reject_frames_device": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, U64, P, P]),
+        "gd_forward_reject_frames": (C.c_int, [P, C.POINTER(gd_forward_batch), U32, P, P, P, P, P, U64, P, P,
+                                               C.POINTER(U64)]),
         "gd_sniff_frames_device": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32]),
         "gd_sniff_frames": (C.c_int, [P, P, U64, P, U32, C.POINTER(gd_sniff_out), U32, C.POINTER(U32)]),
         "gd_cache_invalidate_device": (C.c_int, [P, P, C.POINTER(gd_key_ext), P, U32, P, P]),
@@ -2795,6 +2801,36 @@ class GrainDispatch:
         self._c(lib.gd_forward_frames_device(self.h, C.byref(fb), n, v(d_silo), v(d_act), v(d_status), v(d_placed),
                                              v(d_new_type), v(d_order), v(d_out), out_cap, v(d_out_off),
                                              v(d_fwd_status), v(d_target)))
+
+    def forward_reject_frames(self, batch: dict, info=None, body=None, body_off=None, order=None,
+                              out_cap: Optional[int] = None, out: Optional[np.ndarray] = None):
+        """gd_forward_reject_frames: (out bytes u8[out_cap], out_off u64[n + 1], rej_status u8[n], total).  batch:
+        the keyword arguments of _forward_batch (fwd_silo / fwd_act are ignored)."""
+        fb, n, keep = self._forward_batch(**batch)
+        inf, bo, od = self._opt(info, np.uint32), self._opt(body_off, np.uint64), self._opt(order, np.uint32)
+        bd = None
+        if body is not None and bo is not None:
+            bd = np.frombuffer(bytes(body), dtype=np.uint8) if len(body) else np.zeros(1, dtype=np.uint8)
+        nbody = int(bo[-1]) if bd is not None and len(bo) else 0
+        if out is None:
+            out = np.zeros(2 * len(batch["buf"]) + nbody + n * (90 + 256) if out_cap is None else out_cap, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        st = np.zeros(n, np.uint8)
+        total = C.c_uint64(0)
+        p = lambda a: None if a is None else _ptr(a)
+        self._c(lib.gd_forward_reject_frames(self.h, C.byref(fb), n, p(inf), p(bd), p(bo) if bd is not None else None,
+                                             p(od), _ptr(out) if len(out) else None, len(out), _ptr(out_off),
+                                             _ptr(st), C.byref(total)))
+        return out, out_off, st, int(total.value)
+
+    def forward_reject_frames_device(self, d_batch: dict, n: int, d_info: Optional[int], d_body: Optional[int],
+                                     d_body_off: Optional[int], d_order: Optional[int], d_out: int, out_cap: int,
+                                     d_out_off: int, d_rej_status: int):
+        """d_batch: device addresses under _forward_batch's names, plus buf_len."""
+        fb = self._forward_batch_device(d_batch)
+        v = lambda x: C.c_void_p(x or 0)
+        self._c(lib.gd_forward_reject_frames_device(self.h, C.byref(fb), n, v(d_info), v(d_body), v(d_body_off),
+                                                    v(d_order), v(d_out), out_cap, v(d_out_off), v(d_rej_status)))
 
     def forward_send(self, batch: dict, out_cap: Optional[int] = None, out: Optional[np.ndarray] = None) -> dict:
         """gd_forward_send: plan + route + sender queues + writer; a dict of every stage's outputs."""
