@@ -23,11 +23,6 @@ int encode_bound(gd_handle* h, uint64_t buf_len, uint32_t n, uint64_t* bound) {
     return GD_OK;
 }
 
-EncTab enc_tab(gd_handle* h) {
-    return EncTab{(const uint64_t*)h->act_ids.p, h->n_act_ids, (const uint32_t*)h->enc_tab[0].p, h->enc_nsilos,
-                  (const uint8_t*)h->enc_tab[1].p, (const uint32_t*)h->enc_tab[2].p, h->enc_ntypes};
-}
-
 // The stage on device arrays (placed / new_type / order may be null); enqueue only.
 int encode_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint64_t* frame_off, uint32_t n,
                   const uint32_t* silo, const uint32_t* act, const uint8_t* status, const uint8_t* placed,
@@ -38,9 +33,7 @@ int encode_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint
         return GD_OK;
     }
     StageTime stage(h, "stage:encode");
-    GD_TRY(ensure(h, h->enc_scr[0], (size_t)n * sizeof(EncPlan)));
-    GD_TRY(ensure(h, h->enc_scr[1], (size_t)n * 4));
-    GD_TRY(ensure(h, h->enc_scr[2], ((size_t)n + 1) * 4 + 16));
+    GD_TRY(frameout_scratch(h, h->enc_scr, n, sizeof(EncPlan)));
     EncPlan* plan = (EncPlan*)h->enc_scr[0].p;
     uint32_t* lens = (uint32_t*)h->enc_scr[1].p;
     uint32_t* offs = (uint32_t*)h->enc_scr[2].p;
@@ -51,11 +44,7 @@ int encode_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uint
     else
         GD_TRY(launch(h, "k_enc_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_enc_plan<false>, buf, buf_len,
                       frame_off, n, silo, act, status, placed, new_type, t, plan, lens, enc_status));
-    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
-                  (const uint32_t*)lens, order, n, offs));
-    GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "encode"));
-    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
-                  (const uint32_t*)offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+    GD_TRY(frameout_offsets(h, lens, order, n, offs, out_cap, out_off, "encode"));
     const EncArgs a{buf, frame_off, silo, act, new_type, order, plan, offs, n, out_cap};
     return launch(h, "k_enc_write", dim3(blocks_for(bound + 16, ENC_TILE_CHUNKS * 16)), dim3(BLOCK), 0, k_enc_write, a, t,
                   out);
@@ -156,15 +145,7 @@ int gd_encode_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const u
     GD_TRY(io.status());
     GD_TRY(encode_device(h, dbuf, buf_len, dfoff, n, dsilo, dact, dstatus, dplaced, dtype, dorder, dout, cap, dooff,
                          denc, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap)
-        GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    const int rc = sync_checked(h);                                // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
-    if (rc != GD_OK) return rc;
-    return GD_OK;
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 }  // extern "C"

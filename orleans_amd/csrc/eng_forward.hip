@@ -39,11 +39,6 @@ int forward_bound(gd_handle* h, uint64_t buf_len, uint32_t n, uint64_t* bound) {
     return GD_OK;
 }
 
-EncTab fwd_tab(gd_handle* h) {
-    return EncTab{(const uint64_t*)h->act_ids.p, h->n_act_ids, (const uint32_t*)h->enc_tab[0].p, h->enc_nsilos,
-                  (const uint8_t*)h->enc_tab[1].p, (const uint32_t*)h->enc_tab[2].p, h->enc_ntypes};
-}
-
 struct FwdScratch {
     FwdPlan* plan;
     uint32_t* lens;
@@ -51,9 +46,7 @@ struct FwdScratch {
 };
 
 int forward_scratch(gd_handle* h, uint32_t n, FwdScratch* s) {
-    GD_TRY(ensure(h, h->fwd_scr[0], (size_t)n * sizeof(FwdPlan)));
-    GD_TRY(ensure(h, h->fwd_scr[1], (size_t)n * 4));
-    GD_TRY(ensure(h, h->fwd_scr[2], ((size_t)n + 1) * 4 + 16));
+    GD_TRY(frameout_scratch(h, h->fwd_scr, n, sizeof(FwdPlan)));
     s->plan = (FwdPlan*)h->fwd_scr[0].p;
     s->lens = (uint32_t*)h->fwd_scr[1].p;
     s->offs = (uint32_t*)h->fwd_scr[2].p;
@@ -74,15 +67,11 @@ FwdIn fwd_in(const gd_forward_batch* b, const uint8_t* kind, const uint32_t* old
 int forward_write(gd_handle* h, const uint8_t* buf, const uint64_t* frame_off, uint32_t n, uint32_t local_silo,
                   const FwdScratch& s, const uint32_t* order, uint8_t* out, uint64_t out_cap, uint64_t* out_off,
                   uint64_t write_bound) {
-    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
-                  (const uint32_t*)s.lens, order, n, s.offs));
-    GD_TRY(scan_device<OpAdd>(h, s.offs, n + 1, false, false, "forward"));
-    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
-                  (const uint32_t*)s.offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+    GD_TRY(frameout_offsets(h, s.lens, order, n, s.offs, out_cap, out_off, "forward"));
     const FwdArgs a{buf, frame_off, order, s.plan, s.offs, (const uint8_t*)h->act_ids.p,
                     (const uint8_t*)h->enc_tab[0].p, (const uint8_t*)h->enc_tab[1].p, local_silo, n, out_cap};
     return launch(h, "k_fwd_write", dim3(blocks_for(write_bound + 16, ENC_TILE_CHUNKS * 16)), dim3(BLOCK), 0,
-                  k_fwd_write, a, out);
+                  k_run_write<FwdArgs>, a, out);
 }
 
 // The stage on device arrays; enqueue only.
@@ -97,7 +86,7 @@ int forward_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uin
     FwdScratch s;
     GD_TRY(forward_scratch(h, n, &s));
     GD_TRY(launch(h, "k_fwd_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_fwd_plan, buf, buf_len, frame_off, n,
-                  in, fwd_tab(h), s.plan, s.lens, fwd_status, (uint64_t*)target));
+                  in, enc_tab(h), s.plan, s.lens, fwd_status, (uint64_t*)target));
     return forward_write(h, buf, frame_off, n, in.local_silo, s, order, out, out_cap, out_off, write_bound);
 }
 
@@ -119,7 +108,7 @@ int forward_send_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, cons
     in.silo = nullptr, in.act = nullptr, in.status = nullptr, in.placed = nullptr, in.new_type = nullptr;
     in.ttl = (long long*)h->fwd_scr[3].p;
     in.category = (uint8_t*)h->fwd_scr[4].p;
-    const EncTab t = fwd_tab(h);
+    const EncTab t = enc_tab(h);
     GD_TRY(launch(h, "k_fwd_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_fwd_plan, buf, buf_len, frame_off, n,
                   in, t, s.plan, s.lens, fwd_status, (uint64_t*)target));
     GD_TRY(route_device(h, target, n, silo, act, status));
@@ -236,12 +225,7 @@ int gd_forward_frames(gd_handle* h, const gd_forward_batch* batch, uint32_t n, c
     GD_TRY(io.status());
     const FwdIn in = fwd_in(batch, dkind, dold, dfs, dfa, dsilo, dact, dstatus, dplaced, dtype);
     GD_TRY(forward_device(h, dbuf, batch->buf_len, dfoff, n, in, dorder, dout, cap, dooff, dst, dtg, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);                                        // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 int gd_forward_send(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uint32_t* out_silo, uint32_t* out_act,
@@ -282,12 +266,7 @@ int gd_forward_send(gd_handle* h, const gd_forward_batch* batch, uint32_t n, uin
     const FwdIn in = fwd_in(batch, dkind, dold, dfs, dfa, nullptr, nullptr, nullptr, nullptr, nullptr);
     GD_TRY(forward_send_device(h, dbuf, batch->buf_len, dfoff, n, in, dsilo, dact, dstatus, dsst, dq, dperm, doffs,
                                dout, cap, dooff, dst, dtg, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 }  // extern "C"

@@ -47,27 +47,19 @@ int reject_device(gd_handle* h, const gd_forward_batch* b, const uint8_t* buf, c
     }
     StageTime stage(h, "stage:forward_reject");
     // + 16: k_rej_write reads whole dwords around the record bytes it copies
-    GD_TRY(ensure(h, h->rej_scr[0], (size_t)n * REJ_PLAN_DW * 4 + 16));
-    GD_TRY(ensure(h, h->rej_scr[1], (size_t)n * 4));
-    GD_TRY(ensure(h, h->rej_scr[2], ((size_t)n + 1) * 4 + 16));
+    GD_TRY(frameout_scratch(h, h->rej_scr, n, REJ_PLAN_DW * 4, 16));
     uint32_t* plan = (uint32_t*)h->rej_scr[0].p;
     uint32_t* lens = (uint32_t*)h->rej_scr[1].p;
     uint32_t* offs = (uint32_t*)h->rej_scr[2].p;
     if (!body || !body_off) body = nullptr, body_off = nullptr;
     const RejIn in{kind, old_act, info, body_off, (const uint32_t*)h->rsp_tab[1].p, h->rsp_ninfo,
                    b->max_forward_count, b->local_silo};
-    const EncTab t{(const uint64_t*)h->act_ids.p, h->n_act_ids, (const uint32_t*)h->enc_tab[0].p, h->enc_nsilos,
-                   (const uint8_t*)h->enc_tab[1].p, (const uint32_t*)h->enc_tab[2].p, h->enc_ntypes};
     GD_TRY(launch(h, "k_rej_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_rej_plan, buf, b->buf_len, frame_off,
-                  n, in, t, plan, lens, rej_status));
-    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
-                  (const uint32_t*)lens, order, n, offs));
-    GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "forward_reject"));
-    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
-                  (const uint32_t*)offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+                  n, in, enc_tab(h), plan, lens, rej_status));
+    GD_TRY(frameout_offsets(h, lens, order, n, offs, out_cap, out_off, "forward_reject"));
     const RejArgs a{buf, frame_off, body, body_off, order, plan, offs, (const uint8_t*)h->rsp_tab[0].p, n, out_cap};
     return launch(h, "k_rej_write", dim3(blocks_for(write_bound + 16, ENC_TILE_CHUNKS * 16)), dim3(BLOCK), 0,
-                  k_rej_write, a, out);
+                  k_run_write<RejArgs>, a, out);
 }
 
 }  // namespace
@@ -128,12 +120,7 @@ int gd_forward_reject_frames(gd_handle* h, const gd_forward_batch* batch, uint32
     GD_TRY(io.status());
     GD_TRY(reject_device(h, batch, dbuf, dfoff, dkind, dold, n, dinfo, dbody, dboff, dorder, dout, cap, dooff, dst,
                          bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);                                        // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 }  // extern "C"

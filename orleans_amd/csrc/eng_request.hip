@@ -45,9 +45,8 @@ int request_bound(gd_handle* h, uint32_t n, uint64_t extra, uint64_t* bound) {
 }
 
 ReqTab req_tab(gd_handle* h) {
-    return ReqTab{EncTab{(const uint64_t*)h->act_ids.p, h->n_act_ids, (const uint32_t*)h->enc_tab[0].p, h->enc_nsilos,
-                         (const uint8_t*)h->enc_tab[1].p, (const uint32_t*)h->enc_tab[2].p, h->enc_ntypes},
-                  (const uint8_t*)h->req_tab[0].p, (const uint32_t*)h->req_tab[1].p, h->req_nstr, h->cfg.my_silo};
+    return ReqTab{enc_tab(h), (const uint8_t*)h->req_tab[0].p, (const uint32_t*)h->req_tab[1].p, h->req_nstr,
+                  h->cfg.my_silo};
 }
 
 // The batch as the kernels take it, from pointers that are all device pointers (tx / sx: null or the KeyExt arrays).
@@ -78,20 +77,14 @@ int request_device(gd_handle* h, const ReqIn& in, uint32_t n, const uint32_t* or
         return GD_OK;
     }
     StageTime stage(h, "stage:request");
-    GD_TRY(ensure(h, h->req_scr[0], (size_t)n * sizeof(ReqPlan)));
-    GD_TRY(ensure(h, h->req_scr[1], (size_t)n * 4));
-    GD_TRY(ensure(h, h->req_scr[2], ((size_t)n + 1) * 4 + 16));
+    GD_TRY(frameout_scratch(h, h->req_scr, n, sizeof(ReqPlan)));
     ReqPlan* plan = (ReqPlan*)h->req_scr[0].p;
     uint32_t* lens = (uint32_t*)h->req_scr[1].p;
     uint32_t* offs = (uint32_t*)h->req_scr[2].p;
     const ReqTab t = req_tab(h);
     GD_TRY(launch(h, "k_req_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_req_plan, in, t, n, plan, lens,
                   req_status));
-    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
-                  (const uint32_t*)lens, order, n, offs));
-    GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "request"));
-    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
-                  (const uint32_t*)offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+    GD_TRY(frameout_offsets(h, lens, order, n, offs, out_cap, out_off, "request"));
     const ReqArgs a{in, order, plan, offs, n, out_cap};
     return launch(h, "k_req_write", dim3(blocks_for(write_bound + 16, REQ_TILE)), dim3(BLOCK), 0, k_req_write, a, t,
                   out);
@@ -267,12 +260,7 @@ int gd_request_frames(gd_handle* h, const gd_request_batch* batch, uint32_t n, c
     GD_TRY(io.status());
     const ReqIn in = req_in(&s.d, s.ptx, s.psx, s.body, s.body_off, dsilo, dact, dstatus, dplaced, dtype);
     GD_TRY(request_device(h, in, n, dorder, dout, cap, dooff, dst, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);                                        // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uint32_t* out_silo, uint32_t* out_act,
@@ -310,12 +298,7 @@ int gd_request_send(gd_handle* h, const gd_request_batch* batch, uint32_t n, uin
     GD_TRY(request_send_queues(h, &s.d, s.d.options, n, dsilo, dstatus, dsst, dq, dperm, doffs));
     const ReqIn in = req_in(&s.d, s.ptx, s.psx, s.body, s.body_off, dsilo, dact, dstatus, nullptr, nullptr);
     GD_TRY(request_device(h, in, n, dperm, dout, cap, dooff, dst, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 }  // extern "C"

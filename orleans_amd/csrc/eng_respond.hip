@@ -34,9 +34,7 @@ int respond_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uin
         return GD_OK;
     }
     StageTime stage(h, "stage:respond");
-    GD_TRY(ensure(h, h->rsp_scr[0], (size_t)n * sizeof(RspPlan)));
-    GD_TRY(ensure(h, h->rsp_scr[1], (size_t)n * 4));
-    GD_TRY(ensure(h, h->rsp_scr[2], ((size_t)n + 1) * 4 + 16));
+    GD_TRY(frameout_scratch(h, h->rsp_scr, n, sizeof(RspPlan)));
     RspPlan* plan = (RspPlan*)h->rsp_scr[0].p;
     uint32_t* lens = (uint32_t*)h->rsp_scr[1].p;
     uint32_t* offs = (uint32_t*)h->rsp_scr[2].p;
@@ -48,14 +46,10 @@ int respond_device(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const uin
     else
         GD_TRY(launch(h, "k_rsp_plan", dim3(blocks_for(n, BLOCK)), dim3(BLOCK), 0, k_rsp_plan<false>, buf, buf_len,
                       frame_off, n, in, plan, lens, rsp_status));
-    GD_TRY(launch(h, "k_enc_lens", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_lens,
-                  (const uint32_t*)lens, order, n, offs));
-    GD_TRY(scan_device<OpAdd>(h, offs, n + 1, false, false, "respond"));
-    GD_TRY(launch(h, "k_enc_finish", dim3(blocks_for((uint64_t)n + 1, BLOCK)), dim3(BLOCK), 0, k_enc_finish,
-                  (const uint32_t*)offs, n, out_cap, (unsigned long long*)out_off, &h->ctr->err));
+    GD_TRY(frameout_offsets(h, lens, order, n, offs, out_cap, out_off, "respond"));
     const RspArgs a{buf, frame_off, body, body_off, order, plan, offs, (const uint8_t*)h->rsp_tab[0].p, n, out_cap};
     return launch(h, "k_rsp_write", dim3(blocks_for(write_bound + 16, ENC_TILE_CHUNKS * 16)), dim3(BLOCK), 0,
-                  k_rsp_write, a, out);
+                  k_run_write<RspArgs>, a, out);
 }
 
 int check_respond_args(gd_handle* h, const void* buf, const void* off, uint32_t n, const void* kind, const void* out,
@@ -222,12 +216,7 @@ int gd_respond_frames(gd_handle* h, const uint8_t* buf, uint64_t buf_len, const 
     GD_TRY(io.status());
     GD_TRY(respond_device(h, dbuf, buf_len, dfoff, n, dkind, dres, drej, dinfo, dbody, dboff, dorder, dout, cap, dooff,
                           dst, bound));
-    GD_TRY(io.fetch());
-    GD_TRY(sync(h));
-    const uint64_t total = out_off[n];
-    if (out_total) *out_total = total;
-    if (total && total <= cap) GD_TRY(io.fetch(out_buf, dout, (size_t)total));
-    return sync_checked(h);                                        // a total past out_cap: ERR_ENC_FULL -> GD_EFULL
+    return frameout_fetch(h, io, out_off, n, out_buf, dout, cap, out_total);
 }
 
 }  // extern "C"

@@ -72,6 +72,13 @@ struct EncTab {
     uint32_t n_types;
 };
 
+// Activation index a has an ActivationId.
+__device__ __forceinline__ bool enc_has_id(const EncTab& t, uint32_t a) {
+    if ((uint64_t)a >= t.n_act_ids) return false;
+    const uint64_t* id = t.act_ids + 3ull * a;
+    return (id[0] | id[1] | id[2]) != 0;
+}
+
 // The plan in output coordinates: the starts of the four new fields, their lengths and the source shift behind each.
 struct EncMap {
     uint32_t o_inp, o_ngt, o_ta, o_ts;
@@ -230,11 +237,7 @@ static __global__ __launch_bounds__(BLOCK) void k_enc_plan(const uint8_t* __rest
                     hw.take(ENC_TS_LEN);
                 }
                 const uint32_t a = act[i], s = silo[i];
-                bool has_id = false;
-                if ((uint64_t)a < t.n_act_ids) {
-                    const uint64_t* id = t.act_ids + 3ull * a;
-                    has_id = (id[0] | id[1] | id[2]) != 0;
-                }
+                const bool has_id = enc_has_id(t, a);
                 if (hw.bad) {
                     st = ENC_MALFORMED;
                 } else if (s >= t.n_silos) {

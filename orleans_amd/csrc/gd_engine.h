@@ -41,6 +41,10 @@
 #include "gd_mbsort.h"
 #include "graindispatch.h"
 
+namespace gd {
+struct EncTab;      // gd_encode.h
+}
+
 using namespace gd;
 
 namespace gdx {
@@ -558,6 +562,20 @@ void stage_frame_outputs(HostStage& io, uint32_t n, const gd_frame_fields* want,
                          gd_frame_fields* dev, gd_frame_turn_fields* tdev);
 int frame_scratch(gd_handle* h, uint32_t n, const gd_frame_fields* want, gd_frame_fields* dev);
 int frame_results(gd_handle* h, uint32_t n, const gd_frame_fields* want, const gd_frame_fields* dev);
+// ---- the stages that write frames into one contiguous output (eng_frameout.hip)
+// The ActivationIds, wire silos and grain-class names of gd_encode_configure as the kernels take them.
+EncTab enc_tab(gd_handle* h);
+// A stage's scratch: scr[0] n plan records of plan_bytes (+ plan_pad, where the writer reads past them), scr[1] n
+// output lengths, scr[2] n + 1 scanned offsets (+ 16 bytes of slack).
+int frameout_scratch(gd_handle* h, DevBuf* scr, uint32_t n, size_t plan_bytes, size_t plan_pad = 0);
+// offs[j] = the first output byte of frame order[j] (order null: j), offs[n] the total, from the planner's lens;
+// out_off the same as u64; ERR_ENC_FULL when the total exceeds out_cap.  tag names the scan's profile row.
+int frameout_offsets(gd_handle* h, const uint32_t* lens, const uint32_t* order, uint32_t n, uint32_t* offs,
+                     uint64_t out_cap, uint64_t* out_off, const char* tag);
+// The end of a host-pointer call: io's outputs (out_off among them) come down, then the out_off[n] bytes of d_out
+// when they fit cap; *out_total = out_off[n].  Returns sync_checked's result.
+int frameout_fetch(gd_handle* h, HostStage& io, const uint64_t* out_off, uint32_t n, uint8_t* out_buf,
+                   const uint8_t* d_out, uint64_t cap, uint64_t* out_total);
 int bucket_lsd(gd_handle* h, const uint32_t* acts, uint32_t n, uint32_t n_act, uint32_t* perm, uint32_t* offsets,
                uint32_t* rank_out);
 bool msd3_split(uint32_t n_act, uint32_t* a_out, uint32_t* ra_out);

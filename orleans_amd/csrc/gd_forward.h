@@ -26,12 +26,9 @@
 //   k_fwd_merge, k_fwd_finish   the chain (gd_forward_send*): the route's results merged with the forwarding
 //                 addresses, then the plans of the frames the route hit finished (fwd_place)
 //   k_enc_lens, scan_device, k_enc_finish (gd_frameout.h): the offsets and the capacity check, as the encoder
-//   k_fwd_write   the hot path, cut as k_rsp_write (gd_respond.h): 16-KiB tiles of 16-B chunks at absolute 16-B
-//                 addresses, one owner a chunk, the chunk resolved against the FWD_SEGS run starts (registers) --
-//                 16 B inside one run: one 16-B load + alignbyte; else dword by dword, bytes only for a dword that
-//                 straddles a run edge or a frame boundary -- and one aligned 16-B store a chunk; byte stores only
-//                 at the two ends of the whole output.  The TargetGrain run is read twice: into the appended
-//                 entry and in its own place.
+//   k_fwd_write   the hot path: k_run_write<FwdArgs> (gd_frameout.h), the writer the response and the rejection
+//                 stage use too.  FwdArgs::frame maps a plan record to the FWD_SEGS runs.  The TargetGrain run is
+//                 read twice: into the appended entry and in its own place.
 //
 // Totals are 32-bit: the host refuses (GD_EINVAL) a call whose bound reaches 2^32, so gd_scan.h's scan serves.
 #pragma once
@@ -43,7 +40,6 @@
 #include "gd_frameout.h"
 #include "gd_frames.h"
 #include "gd_hash.h"
-#include "gd_respond.h"
 
 namespace gd {
 
@@ -101,18 +97,12 @@ __device__ __forceinline__ void fwd_plan_store(FwdPlan* dst, const FwdPlan& p) {
     pp[7] = make_uint4(p.type_len, p.flags, p.r_ngt, 0u);
 }
 
-__device__ __forceinline__ bool fwd_has_id(const EncTab& t, uint32_t a) {
-    if ((uint64_t)a >= t.n_act_ids) return false;
-    const uint64_t* id = t.act_ids + 3ull * a;
-    return (id[0] | id[1] | id[2]) != 0;
-}
-
 // Message.SetTargetPlacement (Message.cs:629-639) on the plan of a frame that left k_fwd_plan unaddressed: exactly
 // gd_encode_frames' rule.  Returns the frame's status; the plan changes only with FWDST_OK_ADDRESSED.
 __device__ __forceinline__ uint32_t fwd_place(FwdPlan& p, uint32_t silo, uint32_t act, uint32_t placed, uint32_t ty,
                                               const EncTab& t) {
     if (silo >= t.n_silos) return FWDST_NO_SILO;
-    if (!fwd_has_id(t, act)) return FWDST_NO_ID;
+    if (!enc_has_id(t, act)) return FWDST_NO_ID;
     uint32_t grow = ENC_TA_LEN + ENC_TS_LEN;
     p.flags |= FF_TA | FF_TS;
     p.ta_act = act;
@@ -323,11 +313,11 @@ static __global__ __launch_bounds__(BLOCK) void k_fwd_plan(const uint8_t* __rest
                 st = FWDST_REJECT;                           // MayForward (:627-630)
             } else if (append && in.local_silo >= t.n_silos) {
                 st = FWDST_NO_SILO;
-            } else if (append && !fwd_has_id(t, oa)) {
+            } else if (append && !enc_has_id(t, oa)) {
                 st = FWDST_NO_ID;
             } else if (has_fwd && fs >= t.n_silos) {
                 st = FWDST_NO_SILO;
-            } else if (has_fwd && !fwd_has_id(t, fa)) {
+            } else if (has_fwd && !enc_has_id(t, fa)) {
                 st = FWDST_NO_ID;
             } else {
                 const uint32_t src_len = 8u + (uint32_t)hl + (uint32_t)bl;
@@ -452,8 +442,9 @@ static __global__ __launch_bounds__(BLOCK) void k_fwd_finish(const uint32_t* __r
     fwd_status[i] = (uint8_t)st;
 }
 
-// ------------------------------------------------------------------ k_fwd_write
+// ------------------------------------------------------------------ k_fwd_write: k_run_write<FwdArgs>
 struct FwdArgs {
+    static constexpr uint32_t SEGS = FWD_SEGS;
     const uint8_t* buf;
     const uint64_t* frame_off;
     const uint32_t* order;
@@ -465,152 +456,40 @@ struct FwdArgs {
     uint32_t local_silo;
     uint32_t n;
     uint64_t out_cap;
-};
 
-// One output frame as k_fwd_write sees it: run k holds the output positions [st[k], st[k + 1]) (st[FWD_SEGS] = the
-// frame's end) and output position x of it is the byte at address a_k + x, a_k = d[0] + ... + d[k] (differences,
-// summed under the comparisons, as gd_respond.h's RspFrame).
-struct FwdFrame {
-    uint32_t st[FWD_SEGS];
-    uint64_t d[FWD_SEGS];
-};
-
-// Output frame j, whose first output position is fo.
-__device__ __forceinline__ void fwd_frame(const FwdArgs& a, uint32_t j, uint32_t fo, FwdFrame& f) {
-    const uint32_t i = a.order ? min(a.order[j], a.n - 1) : j;
-    const uint4* pp = reinterpret_cast<const uint4*>(a.plan + i);
-    const uint4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q6 = pp[6], q7 = pp[7];
-    const uint64_t src = reinterpret_cast<uint64_t>(a.buf + a.frame_off[i]);
-    const uint64_t cb = reinterpret_cast<uint64_t>(a.plan + i) + 2 * FWD_RUNS * 4;        // FwdPlan::c
-    const uint64_t ids = reinterpret_cast<uint64_t>(a.act_ids), silos = reinterpret_cast<uint64_t>(a.silo_wire);
-    const uint32_t fl = q7.y;
-    const uint32_t ap = (fl & FF_APPEND) ? 1u : 0u, ta = (fl & FF_TA) ? 1u : 0u, ts = (fl & FF_TS) ? 1u : 0u;
-    uint32_t cur = fo;
-    uint64_t prev = 0;
-#define seg(k, from, len)             \
-    f.st[k] = cur;                    \
-    f.d[k] = ((from) - cur) - prev;   \
-    prev = (from) - cur;              \
-    cur += (len)
-    seg(0, cb, 12u + ((fl & FF_COUNT) ? 4u : 0u));
-    seg(1, src + q0.x, q2.x);
-    seg(2, silos + 24ull * a.local_silo, 24u * ap);
-    seg(3, src + q0.y, q2.y);
-    seg(4, ids + 24ull * q6.x, 24u * ap);
-    seg(5, cb + 28, 4u * ap);
-    seg(6, src + q0.z, q2.z);
-    seg(7, cb + 16, (fl & FF_FC) ? 4u : 0u);
-    seg(8, src + q0.w, q2.w);
-    seg(9, cb + 20, (fl & FF_INP) ? 1u : 0u);
-    seg(10, src + q1.x, q3.x);
-    seg(11, cb + 24, (fl & FF_NGT) ? 4u : 0u);
-    seg(12, reinterpret_cast<uint64_t>(a.type_utf8) + q6.w, (fl & FF_NGT) ? q7.x : 0u);
-    seg(13, src + q1.y, q3.y);
-    seg(14, ids + 24ull * q6.y, 24u * ta);
-    seg(15, cb + 28, 4u * ta);
-    seg(16, src + q1.z, q3.z);
-    seg(17, silos + 24ull * q6.z, 24u * ts);
-    seg(18, src + q1.w, q3.w);
-#undef seg
-}
-
-// The address of the byte at output position x, and *same = [x, x + span] lies in one run.
-__device__ __forceinline__ uint64_t fwd_addr(const FwdFrame& f, uint32_t x, uint32_t span, bool* same) {
-    uint64_t a = f.d[0];
-    uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < FWD_SEGS; ++k) {
-        const bool in = x >= f.st[k];
-        a += in ? f.d[k] : 0ull;
-        c0 += in ? 1u : 0u;
-        c1 += (x + span >= f.st[k]) ? 1u : 0u;
+    // Output frame j, whose first output position is fo.
+    __device__ __forceinline__ void frame(uint32_t j, uint32_t fo, RunFrame<SEGS>& f) const {
+        const uint32_t i = order ? min(order[j], n - 1) : j;
+        const uint4* pp = reinterpret_cast<const uint4*>(plan + i);
+        const uint4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q6 = pp[6], q7 = pp[7];
+        const uint64_t src = reinterpret_cast<uint64_t>(buf + frame_off[i]);
+        const uint64_t cb = reinterpret_cast<uint64_t>(plan + i) + 2 * FWD_RUNS * 4;      // FwdPlan::c
+        const uint64_t ids = reinterpret_cast<uint64_t>(act_ids), silos = reinterpret_cast<uint64_t>(silo_wire);
+        const uint32_t fl = q7.y;
+        const uint32_t ap = (fl & FF_APPEND) ? 1u : 0u, ta = (fl & FF_TA) ? 1u : 0u, ts = (fl & FF_TS) ? 1u : 0u;
+        uint32_t cur = fo;
+        uint64_t prev = 0;
+        RUN_SEG(f, cur, prev, 0, cb, 12u + ((fl & FF_COUNT) ? 4u : 0u));
+        RUN_SEG(f, cur, prev, 1, src + q0.x, q2.x);
+        RUN_SEG(f, cur, prev, 2, silos + 24ull * local_silo, 24u * ap);
+        RUN_SEG(f, cur, prev, 3, src + q0.y, q2.y);
+        RUN_SEG(f, cur, prev, 4, ids + 24ull * q6.x, 24u * ap);
+        RUN_SEG(f, cur, prev, 5, cb + 28, 4u * ap);
+        RUN_SEG(f, cur, prev, 6, src + q0.z, q2.z);
+        RUN_SEG(f, cur, prev, 7, cb + 16, (fl & FF_FC) ? 4u : 0u);
+        RUN_SEG(f, cur, prev, 8, src + q0.w, q2.w);
+        RUN_SEG(f, cur, prev, 9, cb + 20, (fl & FF_INP) ? 1u : 0u);
+        RUN_SEG(f, cur, prev, 10, src + q1.x, q3.x);
+        RUN_SEG(f, cur, prev, 11, cb + 24, (fl & FF_NGT) ? 4u : 0u);
+        RUN_SEG(f, cur, prev, 12, reinterpret_cast<uint64_t>(type_utf8) + q6.w, (fl & FF_NGT) ? q7.x : 0u);
+        RUN_SEG(f, cur, prev, 13, src + q1.y, q3.y);
+        RUN_SEG(f, cur, prev, 14, ids + 24ull * q6.y, 24u * ta);
+        RUN_SEG(f, cur, prev, 15, cb + 28, 4u * ta);
+        RUN_SEG(f, cur, prev, 16, src + q1.z, q3.z);
+        RUN_SEG(f, cur, prev, 17, silos + 24ull * q6.z, 24u * ts);
+        RUN_SEG(f, cur, prev, 18, src + q1.w, q3.w);
     }
-    *same = c0 == c1;
-    return a + x;
-}
-
-static __global__ __launch_bounds__(BLOCK) void k_fwd_write(FwdArgs a, uint8_t* __restrict__ out) {
-    __shared__ uint32_t s_off[ENC_TILE_FRAMES + 1];
-    __shared__ uint32_t s_rng[2];
-    const uint32_t n = a.n;
-    const uint32_t total = a.offs[n];
-    if (total == 0 || (uint64_t)total > a.out_cap) return;          // too long: k_enc_finish raised ERR_ENC_FULL
-    // chunk c holds output positions [16 c - lead, 16 c - lead + 16): absolute 16-B addresses
-    const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-    const uint64_t t0 = (uint64_t)blockIdx.x * ENC_TILE_CHUNKS * 16;          // in lead-shifted coordinates
-    if (t0 >= (uint64_t)total + lead) return;
-    const uint32_t first = (uint32_t)(t0 > lead ? t0 - lead : 0);              // the tile's first output position
-    const uint64_t t1 = t0 + (uint64_t)ENC_TILE_CHUNKS * 16 - lead;
-    const uint32_t last = (uint32_t)(t1 < total ? t1 : total) - 1;            // ... and its last
-    if (threadIdx.x < 2) s_rng[threadIdx.x] = enc_find(a.offs, 0, 0, n - 1, threadIdx.x ? last : first);
-    __syncthreads();
-    const uint32_t jlo = s_rng[0], jhi = s_rng[1];
-    const bool in_lds = jhi - jlo < ENC_TILE_FRAMES;
-    if (in_lds)
-        for (uint32_t k = threadIdx.x; k <= jhi - jlo + 1; k += BLOCK) s_off[k] = a.offs[jlo + k];
-    __syncthreads();
-    const uint32_t* so = in_lds ? s_off : a.offs + jlo;
-
-    for (uint32_t it = 0; it < ENC_TILE_CHUNKS / BLOCK; ++it) {
-        const uint64_t c0 = t0 + 16ull * (it * BLOCK + threadIdx.x);          // lead-shifted start of the chunk
-        if (c0 >= (uint64_t)total + lead) break;
-        const uint32_t x0 = (uint32_t)(c0 > lead ? c0 - lead : 0);
-        const uint64_t c1 = c0 + 16 - lead;
-        const uint32_t x1 = (uint32_t)(c1 < total ? c1 : total);              // the chunk's positions [x0, x1)
-        const bool whole = x1 - x0 == 16;                                      // then out + x0 is 16-B aligned
-        uint32_t j = jlo, fend = 0;                                            // the frame at hand ends at fend
-        FwdFrame f;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        uint32_t x = x0;
-        while (x < x1) {
-            if (x >= fend) {                                                   // zero-length frames are stepped over
-                j = enc_find(so, jlo, j, jhi, x);
-                fend = so[j + 1 - jlo];
-                fwd_frame(a, j, so[j - jlo], f);
-            }
-            const uint32_t k = x - x0, room = min(x1, fend) - x;
-            bool same = false;
-            if (whole && k == 0 && room == 16) {
-                const uint64_t s = fwd_addr(f, x, 15, &same);
-                if (same) {                                                    // one run: 16 source bytes at any alignment
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const EncU4 q = *reinterpret_cast<const EncU4*>(s - sh);
-                    if (sh) {
-                        const uint32_t e = *reinterpret_cast<const uint32_t*>(s - sh + 16);
-                        v.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh);
-                        v.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
-                        v.z = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
-                        v.w = __builtin_amdgcn_alignbyte(e, q.w, sh);
-                    } else {
-                        v = make_uint4(q.x, q.y, q.z, q.w);
-                    }
-                    x += 16;
-                    continue;
-                }
-            }
-            if (whole && (k & 3u) == 0 && room >= 4) {
-                const uint64_t s = fwd_addr(f, x, 3, &same);
-                if (same) {                                                    // a dword inside one run
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const uint32_t* p = reinterpret_cast<const uint32_t*>(s - sh);
-                    uint32_t d = p[0];
-                    if (sh) d = __builtin_amdgcn_alignbyte(p[1], d, sh);
-                    rsp_put(v, k >> 2, d);
-                    x += 4;
-                    continue;
-                }
-            }
-            const uint32_t b = *reinterpret_cast<const uint8_t*>(fwd_addr(f, x, 0, &same));
-            if (whole) {
-                const uint32_t wd = k >> 2, old = wd == 0 ? v.x : wd == 1 ? v.y : wd == 2 ? v.z : v.w;
-                rsp_put(v, wd, old | (b << (8 * (k & 3u))));
-            } else {
-                out[x] = (uint8_t)b;                                           // the first or last chunk of the output
-            }
-            x += 1;
-        }
-        if (whole) *reinterpret_cast<uint4*>(out + x0) = v;
-    }
-}
+};
 
 }  // namespace gd
+

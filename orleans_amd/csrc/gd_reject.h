@@ -34,9 +34,8 @@
 //                 entries as k_fwd_plan, on as k_rsp_plan.  Writes the 192-B record of an OK frame, the output
 //                 length and the status
 //   k_enc_lens, scan_device, k_enc_finish (gd_frameout.h): the offsets and the capacity check, as the encoder
-//   k_rej_write   k_rsp_write / k_fwd_write's contract: 16-KiB tiles of 16-B chunks at absolute 16-B addresses, one
-//                 owner a chunk, one aligned 16-B store a chunk, byte stores only at the two ends of the whole
-//                 output, zero-length frames stepped over, global offsets searched past ENC_TILE_FRAMES
+//   k_rej_write   k_run_write<RejArgs> (gd_frameout.h), the writer the response and the forward stage use too.
+//                 RejArgs::frame maps a plan record to the REJ_SEGS runs
 //
 // Totals are 32-bit: the host refuses (GD_EINVAL) a call whose bound reaches 2^32, so gd_scan.h's scan serves.
 #pragma once
@@ -45,6 +44,7 @@
 #include <cstdint>
 
 #include "gd_forward.h"
+#include "gd_respond.h"
 
 namespace gd {
 
@@ -249,7 +249,7 @@ static __global__ __launch_bounds__(BLOCK) void k_rej_plan(const uint8_t* __rest
             st = FWDREJ_DISCARDED;                               // RejectMessage :209-221: only a Request is answered
         } else if (append && in.local_silo >= t.n_silos) {
             st = FWDREJ_NO_SILO;
-        } else if (append && !fwd_has_id(t, oa)) {
+        } else if (append && !enc_has_id(t, oa)) {
             st = FWDREJ_NO_ID;
         } else {
             st = FWDREJ_OK;
@@ -325,8 +325,9 @@ static __global__ __launch_bounds__(BLOCK) void k_rej_plan(const uint8_t* __rest
     rej_status[i] = (uint8_t)st;
 }
 
-// ------------------------------------------------------------------ k_rej_write
+// ------------------------------------------------------------------ k_rej_write: k_run_write<RejArgs>
 struct RejArgs {
+    static constexpr uint32_t SEGS = REJ_SEGS;
     const uint8_t* buf;
     const uint64_t* frame_off;
     const uint8_t* body;         // may be null (then every body is empty)
@@ -337,145 +338,33 @@ struct RejArgs {
     const uint8_t* info_utf8;
     uint32_t n;
     uint64_t out_cap;
-};
 
-// One output frame as k_rej_write sees it: run k holds the output positions [st[k], st[k + 1]) (st[REJ_SEGS] = the
-// frame's end) and output position x of it is the byte at address a_k + x, a_k = d[0] + ... + d[k] (differences,
-// summed under the comparisons, as gd_respond.h's RspFrame).
-struct RejFrame {
-    uint32_t st[REJ_SEGS];
-    uint64_t d[REJ_SEGS];
-};
-
-// Output frame j, whose first output position is fo.
-__device__ __forceinline__ void rej_frame(const RejArgs& a, uint32_t j, uint32_t fo, RejFrame& f) {
-    const uint32_t i = a.order ? min(a.order[j], a.n - 1) : j;
-    const uint4* pp = reinterpret_cast<const uint4*>(a.plan + (uint64_t)REJ_PLAN_DW * i);
-    const uint4 q0 = pp[0], q8 = pp[8], q9 = pp[9], q10 = pp[10], q11 = pp[11];
-    const uint64_t src = reinterpret_cast<uint64_t>(a.buf + a.frame_off[i]);
-    const uint64_t cb = reinterpret_cast<uint64_t>(pp);
-    const uint64_t body = a.body ? reinterpret_cast<uint64_t>(a.body + a.body_off[i]) : 0ull;
-    uint32_t cur = fo;
-    uint64_t prev = 0;
-#define seg(k, from, len)             \
-    f.st[k] = cur;                    \
-    f.d[k] = ((from) - cur) - prev;   \
-    prev = (from) - cur;              \
-    cur += (len)
-    seg(0, cb + REJ_A, q8.x & 0xFFu);
-    seg(1, src + 16, q9.w);
-    seg(2, cb + REJ_B, (q8.x >> 8) & 0xFFu);
-    seg(3, src + q8.y, q10.x);
-    seg(4, cb + REJ_C, (q8.x >> 16) & 0xFFu);
-    seg(5, src + q8.z, q10.y);
-    seg(6, cb + REJ_D, q8.x >> 24);
-    seg(7, reinterpret_cast<uint64_t>(a.info_utf8) + q11.z, q11.w);
-    seg(8, cb + REJ_E, 1u);
-    seg(9, src + q8.w, q10.z);
-    seg(10, src + q9.x, q10.w);
-    seg(11, src + q9.y, q11.x);
-    seg(12, src + q9.z, q11.y);
-    seg(13, body, q0.y);
-#undef seg
-}
-
-// The address of the byte at output position x, and *same = [x, x + span] lies in one run.
-__device__ __forceinline__ uint64_t rej_addr(const RejFrame& f, uint32_t x, uint32_t span, bool* same) {
-    uint64_t a = f.d[0];
-    uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < REJ_SEGS; ++k) {
-        const bool in = x >= f.st[k];
-        a += in ? f.d[k] : 0ull;
-        c0 += in ? 1u : 0u;
-        c1 += (x + span >= f.st[k]) ? 1u : 0u;
+    // Output frame j, whose first output position is fo.
+    __device__ __forceinline__ void frame(uint32_t j, uint32_t fo, RunFrame<SEGS>& f) const {
+        const uint32_t i = order ? min(order[j], n - 1) : j;
+        const uint4* pp = reinterpret_cast<const uint4*>(plan + (uint64_t)REJ_PLAN_DW * i);
+        const uint4 q0 = pp[0], q8 = pp[8], q9 = pp[9], q10 = pp[10], q11 = pp[11];
+        const uint64_t src = reinterpret_cast<uint64_t>(buf + frame_off[i]);
+        const uint64_t cb = reinterpret_cast<uint64_t>(pp);
+        const uint64_t bd = body ? reinterpret_cast<uint64_t>(body + body_off[i]) : 0ull;
+        uint32_t cur = fo;
+        uint64_t prev = 0;
+        RUN_SEG(f, cur, prev, 0, cb + REJ_A, q8.x & 0xFFu);
+        RUN_SEG(f, cur, prev, 1, src + 16, q9.w);
+        RUN_SEG(f, cur, prev, 2, cb + REJ_B, (q8.x >> 8) & 0xFFu);
+        RUN_SEG(f, cur, prev, 3, src + q8.y, q10.x);
+        RUN_SEG(f, cur, prev, 4, cb + REJ_C, (q8.x >> 16) & 0xFFu);
+        RUN_SEG(f, cur, prev, 5, src + q8.z, q10.y);
+        RUN_SEG(f, cur, prev, 6, cb + REJ_D, q8.x >> 24);
+        RUN_SEG(f, cur, prev, 7, reinterpret_cast<uint64_t>(info_utf8) + q11.z, q11.w);
+        RUN_SEG(f, cur, prev, 8, cb + REJ_E, 1u);
+        RUN_SEG(f, cur, prev, 9, src + q8.w, q10.z);
+        RUN_SEG(f, cur, prev, 10, src + q9.x, q10.w);
+        RUN_SEG(f, cur, prev, 11, src + q9.y, q11.x);
+        RUN_SEG(f, cur, prev, 12, src + q9.z, q11.y);
+        RUN_SEG(f, cur, prev, 13, bd, q0.y);
     }
-    *same = c0 == c1;
-    return a + x;
-}
-
-static __global__ __launch_bounds__(BLOCK) void k_rej_write(RejArgs a, uint8_t* __restrict__ out) {
-    __shared__ uint32_t s_off[ENC_TILE_FRAMES + 1];
-    __shared__ uint32_t s_rng[2];
-    const uint32_t n = a.n;
-    const uint32_t total = a.offs[n];
-    if (total == 0 || (uint64_t)total > a.out_cap) return;          // too long: k_enc_finish raised ERR_ENC_FULL
-    // chunk c holds output positions [16 c - lead, 16 c - lead + 16): absolute 16-B addresses
-    const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-    const uint64_t t0 = (uint64_t)blockIdx.x * ENC_TILE_CHUNKS * 16;          // in lead-shifted coordinates
-    if (t0 >= (uint64_t)total + lead) return;
-    const uint32_t first = (uint32_t)(t0 > lead ? t0 - lead : 0);              // the tile's first output position
-    const uint64_t t1 = t0 + (uint64_t)ENC_TILE_CHUNKS * 16 - lead;
-    const uint32_t last = (uint32_t)(t1 < total ? t1 : total) - 1;            // ... and its last
-    if (threadIdx.x < 2) s_rng[threadIdx.x] = enc_find(a.offs, 0, 0, n - 1, threadIdx.x ? last : first);
-    __syncthreads();
-    const uint32_t jlo = s_rng[0], jhi = s_rng[1];
-    const bool in_lds = jhi - jlo < ENC_TILE_FRAMES;
-    if (in_lds)
-        for (uint32_t k = threadIdx.x; k <= jhi - jlo + 1; k += BLOCK) s_off[k] = a.offs[jlo + k];
-    __syncthreads();
-    const uint32_t* so = in_lds ? s_off : a.offs + jlo;
-
-    for (uint32_t it = 0; it < ENC_TILE_CHUNKS / BLOCK; ++it) {
-        const uint64_t c0 = t0 + 16ull * (it * BLOCK + threadIdx.x);          // lead-shifted start of the chunk
-        if (c0 >= (uint64_t)total + lead) break;
-        const uint32_t x0 = (uint32_t)(c0 > lead ? c0 - lead : 0);
-        const uint64_t c1 = c0 + 16 - lead;
-        const uint32_t x1 = (uint32_t)(c1 < total ? c1 : total);              // the chunk's positions [x0, x1)
-        const bool whole = x1 - x0 == 16;                                      // then out + x0 is 16-B aligned
-        uint32_t j = jlo, fend = 0;                                            // the frame at hand ends at fend
-        RejFrame f;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        uint32_t x = x0;
-        while (x < x1) {
-            if (x >= fend) {                                                   // zero-length frames are stepped over
-                j = enc_find(so, jlo, j, jhi, x);
-                fend = so[j + 1 - jlo];
-                rej_frame(a, j, so[j - jlo], f);
-            }
-            const uint32_t k = x - x0, room = min(x1, fend) - x;
-            bool same = false;
-            if (whole && k == 0 && room == 16) {
-                const uint64_t s = rej_addr(f, x, 15, &same);
-                if (same) {                                                    // one run: 16 source bytes at any alignment
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const EncU4 q = *reinterpret_cast<const EncU4*>(s - sh);
-                    if (sh) {
-                        const uint32_t e = *reinterpret_cast<const uint32_t*>(s - sh + 16);
-                        v.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh);
-                        v.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
-                        v.z = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
-                        v.w = __builtin_amdgcn_alignbyte(e, q.w, sh);
-                    } else {
-                        v = make_uint4(q.x, q.y, q.z, q.w);
-                    }
-                    x += 16;
-                    continue;
-                }
-            }
-            if (whole && (k & 3u) == 0 && room >= 4) {
-                const uint64_t s = rej_addr(f, x, 3, &same);
-                if (same) {                                                    // a dword inside one run
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const uint32_t* p = reinterpret_cast<const uint32_t*>(s - sh);
-                    uint32_t d = p[0];
-                    if (sh) d = __builtin_amdgcn_alignbyte(p[1], d, sh);
-                    rsp_put(v, k >> 2, d);
-                    x += 4;
-                    continue;
-                }
-            }
-            const uint32_t b = *reinterpret_cast<const uint8_t*>(rej_addr(f, x, 0, &same));
-            if (whole) {
-                const uint32_t wd = k >> 2, old = wd == 0 ? v.x : wd == 1 ? v.y : wd == 2 ? v.z : v.w;
-                rsp_put(v, wd, old | (b << (8 * (k & 3u))));
-            } else {
-                out[x] = (uint8_t)b;                                           // the first or last chunk of the output
-            }
-            x += 1;
-        }
-        if (whole) *reinterpret_cast<uint4*>(out + x0) = v;
-    }
-}
+};
 
 }  // namespace gd
+

@@ -135,12 +135,6 @@ __device__ __forceinline__ int32_t req_ext(const int32_t* len, const uint64_t* o
     return fallback ? -1 : l;
 }
 
-__device__ __forceinline__ bool req_has_id(const EncTab& e, uint32_t a) {
-    if ((uint64_t)a >= e.n_act_ids) return false;
-    const uint64_t* id = e.act_ids + 3ull * a;
-    return (id[0] | id[1] | id[2]) != 0;
-}
-
 // The byte length of string idx of a table (0: no index, past the table, or empty).
 __device__ __forceinline__ uint32_t req_str_len(const uint32_t* idx, uint32_t i, const uint32_t* off, uint32_t n_tab) {
     if (!idx) return 0;
@@ -161,9 +155,9 @@ static __global__ __launch_bounds__(BLOCK) void k_req_plan(ReqIn in, ReqTab t, u
     uint32_t st;
     if (fallback) st = REQ_FALLBACK;
     else if ((uint32_t)(in.target[3ull * i + 2] >> 56) == REQ_CAT_SYSTEM_TARGET) st = REQ_FALLBACK;
-    else if (!req_has_id(t.e, in.sender_act[i])) st = REQ_NO_ID;
+    else if (!enc_has_id(t.e, in.sender_act[i])) st = REQ_NO_ID;
     else if (routed && in.silo[i] >= t.e.n_silos) st = REQ_NO_SILO;
-    else if (routed && !req_has_id(t.e, in.act[i])) st = REQ_NO_ID;
+    else if (routed && !enc_has_id(t.e, in.act[i])) st = REQ_NO_ID;
     else st = routed ? REQ_OK : REQ_UNADDRESSED;
 
     ReqPlan p{0, st, 0, 0, -1, -1, 0, 0};

@@ -15,14 +15,9 @@
 //                 128-B RspPlan a frame -- 12 (source position, length) runs in output order and the constants --
 //                 its output length and its status
 //   k_enc_lens, scan_device, k_enc_finish (gd_frameout.h): the offsets and the capacity check, as the encoder
-//   k_rsp_write   the hot path.  The output is cut as k_enc_write cuts it: 16-KiB tiles of 16-B chunks at absolute
-//                 16-B addresses, one chunk a lane and step, one owner a chunk.  A lane turns its frame's plan
-//                 into the RSP_SEGS run starts (prefix sums, registers) and resolves its chunk against them: a
-//                 chunk inside one run (the body, a long string) is one 16-B load (dword aligned + alignbyte); else
-//                 dword by dword, a dword inside one run being two aligned loads and an alignbyte, and only a
-//                 dword that straddles a run edge or a frame boundary is put together from bytes.  The chunk
-//                 leaves as one aligned 16-B store; only the first and last chunk of the whole output use byte
-//                 stores.
+//   k_rsp_write   the hot path: k_run_write<RspArgs> (gd_frameout.h), the writer the forward and the rejection
+//                 stage use too.  RspArgs::frame turns a frame's plan into the RSP_SEGS run starts (prefix sums,
+//                 registers); the writer resolves each 16-B chunk of the output against them.
 //
 // Totals are 32-bit: the host refuses (GD_EINVAL) a call whose bound reaches 2^32, so gd_scan.h's scan serves.
 #pragma once
@@ -401,8 +396,9 @@ static __global__ __launch_bounds__(BLOCK) void k_rsp_plan(const uint8_t* __rest
     rsp_status[i] = (uint8_t)st;
 }
 
-// ------------------------------------------------------------------ k_rsp_write
+// ------------------------------------------------------------------ k_rsp_write: k_run_write<RspArgs>
 struct RspArgs {
+    static constexpr uint32_t SEGS = RSP_SEGS;
     const uint8_t* buf;
     const uint64_t* frame_off;
     const uint8_t* body;         // may be null (then every body is empty)
@@ -413,157 +409,38 @@ struct RspArgs {
     const uint8_t* info_utf8;
     uint32_t n;
     uint64_t out_cap;
-};
 
-// One output frame as k_rsp_write sees it: run k holds the output positions [st[k], st[k + 1]) (st[RSP_SEGS] = the
-// frame's end) and output position x of it is the byte at address a_k + x, a_k = d[0] + ... + d[k].  (Differences,
-// summed under the comparisons: a table of the a_k themselves would be indexed by run and so leave the registers.)
-struct RspFrame {
-    uint32_t st[RSP_SEGS];
-    uint64_t d[RSP_SEGS];
-};
-
-// Output frame j, whose first output position is fo.
-__device__ __forceinline__ void rsp_frame(const RspArgs& a, uint32_t j, uint32_t fo, RspFrame& f) {
-    const uint32_t i = a.order ? min(a.order[j], a.n - 1) : j;
-    const uint4* pp = reinterpret_cast<const uint4*>(a.plan + i);
-    const uint4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q4 = pp[4], q5 = pp[5], q6 = pp[6], q7 = pp[7];
-    const uint64_t src = reinterpret_cast<uint64_t>(a.buf + a.frame_off[i]);
-    const uint64_t cb = reinterpret_cast<uint64_t>(a.plan + i) + 2 * RSP_RUNS * 4;       // RspPlan::c
-    const uint32_t info_len = (q6.w >> 8) | (q7.x << 24), fl = q7.z;
-    const uint64_t body = a.body ? reinterpret_cast<uint64_t>(a.body + a.body_off[i]) : 0ull;
-    uint32_t cur = fo;
-    uint64_t prev = 0;
-#define seg(k, from, len)             \
-    f.st[k] = cur;                    \
-    f.d[k] = ((from) - cur) - prev;   \
-    prev = (from) - cur;              \
-    cur += (len)
-    seg(0, cb, 12);
-    seg(1, src + q0.x, q3.x);
-    seg(2, cb + 12, 1);
-    seg(3, src + q0.y, q3.y);
-    seg(4, src + q0.z, q3.z);
-    seg(5, src + q0.w, q3.w);
-    seg(6, src + q1.x, q4.x);
-    seg(7, cb + 13, (fl & 1u) ? 4u : 0u);
-    seg(8, reinterpret_cast<uint64_t>(a.info_utf8) + q7.y, info_len);
-    seg(9, cb + ((fl & 2u) ? 17 : 18), ((fl >> 1) & 1u) + ((fl >> 2) & 1u));
-    seg(10, src + q1.y, q4.y);
-    seg(11, src + q1.z, q4.z);
-    seg(12, src + q1.w, q4.w);
-    seg(13, src + q2.x, q5.x);
-    seg(14, src + q2.y, q5.y);
-    seg(15, src + q2.z, q5.z);
-    seg(16, src + q2.w, q5.w);
-    seg(17, body, q6.y);
-#undef seg
-}
-
-// The address of the byte at output position x, and *same = [x, x + span] lies in one run.
-__device__ __forceinline__ uint64_t rsp_addr(const RspFrame& f, uint32_t x, uint32_t span, bool* same) {
-    uint64_t a = f.d[0];
-    uint32_t c0 = 0, c1 = 0;
-#pragma unroll
-    for (uint32_t k = 1; k < RSP_SEGS; ++k) {
-        const bool in = x >= f.st[k];
-        a += in ? f.d[k] : 0ull;
-        c0 += in ? 1u : 0u;
-        c1 += (x + span >= f.st[k]) ? 1u : 0u;
+    // Output frame j, whose first output position is fo.
+    __device__ __forceinline__ void frame(uint32_t j, uint32_t fo, RunFrame<SEGS>& f) const {
+        const uint32_t i = order ? min(order[j], n - 1) : j;
+        const uint4* pp = reinterpret_cast<const uint4*>(plan + i);
+        const uint4 q0 = pp[0], q1 = pp[1], q2 = pp[2], q3 = pp[3], q4 = pp[4], q5 = pp[5], q6 = pp[6], q7 = pp[7];
+        const uint64_t src = reinterpret_cast<uint64_t>(buf + frame_off[i]);
+        const uint64_t cb = reinterpret_cast<uint64_t>(plan + i) + 2 * RSP_RUNS * 4;     // RspPlan::c
+        const uint32_t info_len = (q6.w >> 8) | (q7.x << 24), fl = q7.z;
+        const uint64_t bd = body ? reinterpret_cast<uint64_t>(body + body_off[i]) : 0ull;
+        uint32_t cur = fo;
+        uint64_t prev = 0;
+        RUN_SEG(f, cur, prev, 0, cb, 12);
+        RUN_SEG(f, cur, prev, 1, src + q0.x, q3.x);
+        RUN_SEG(f, cur, prev, 2, cb + 12, 1);
+        RUN_SEG(f, cur, prev, 3, src + q0.y, q3.y);
+        RUN_SEG(f, cur, prev, 4, src + q0.z, q3.z);
+        RUN_SEG(f, cur, prev, 5, src + q0.w, q3.w);
+        RUN_SEG(f, cur, prev, 6, src + q1.x, q4.x);
+        RUN_SEG(f, cur, prev, 7, cb + 13, (fl & 1u) ? 4u : 0u);
+        RUN_SEG(f, cur, prev, 8, reinterpret_cast<uint64_t>(info_utf8) + q7.y, info_len);
+        RUN_SEG(f, cur, prev, 9, cb + ((fl & 2u) ? 17 : 18), ((fl >> 1) & 1u) + ((fl >> 2) & 1u));
+        RUN_SEG(f, cur, prev, 10, src + q1.y, q4.y);
+        RUN_SEG(f, cur, prev, 11, src + q1.z, q4.z);
+        RUN_SEG(f, cur, prev, 12, src + q1.w, q4.w);
+        RUN_SEG(f, cur, prev, 13, src + q2.x, q5.x);
+        RUN_SEG(f, cur, prev, 14, src + q2.y, q5.y);
+        RUN_SEG(f, cur, prev, 15, src + q2.z, q5.z);
+        RUN_SEG(f, cur, prev, 16, src + q2.w, q5.w);
+        RUN_SEG(f, cur, prev, 17, bd, q6.y);
     }
-    *same = c0 == c1;
-    return a + x;
-}
-
-__device__ __forceinline__ void rsp_put(uint4& v, uint32_t w, uint32_t val) {
-    v.x = w == 0 ? val : v.x;
-    v.y = w == 1 ? val : v.y;
-    v.z = w == 2 ? val : v.z;
-    v.w = w == 3 ? val : v.w;
-}
-
-static __global__ __launch_bounds__(BLOCK) void k_rsp_write(RspArgs a, uint8_t* __restrict__ out) {
-    __shared__ uint32_t s_off[ENC_TILE_FRAMES + 1];
-    __shared__ uint32_t s_rng[2];
-    const uint32_t n = a.n;
-    const uint32_t total = a.offs[n];
-    if (total == 0 || (uint64_t)total > a.out_cap) return;          // too long: k_enc_finish raised ERR_ENC_FULL
-    // chunk c holds output positions [16 c - lead, 16 c - lead + 16): absolute 16-B addresses
-    const uint32_t lead = (uint32_t)(reinterpret_cast<uintptr_t>(out) & 15u);
-    const uint64_t t0 = (uint64_t)blockIdx.x * ENC_TILE_CHUNKS * 16;          // in lead-shifted coordinates
-    if (t0 >= (uint64_t)total + lead) return;
-    const uint32_t first = (uint32_t)(t0 > lead ? t0 - lead : 0);              // the tile's first output position
-    const uint64_t t1 = t0 + (uint64_t)ENC_TILE_CHUNKS * 16 - lead;
-    const uint32_t last = (uint32_t)(t1 < total ? t1 : total) - 1;            // ... and its last
-    if (threadIdx.x < 2) s_rng[threadIdx.x] = enc_find(a.offs, 0, 0, n - 1, threadIdx.x ? last : first);
-    __syncthreads();
-    const uint32_t jlo = s_rng[0], jhi = s_rng[1];
-    const bool in_lds = jhi - jlo < ENC_TILE_FRAMES;
-    if (in_lds)
-        for (uint32_t k = threadIdx.x; k <= jhi - jlo + 1; k += BLOCK) s_off[k] = a.offs[jlo + k];
-    __syncthreads();
-    const uint32_t* so = in_lds ? s_off : a.offs + jlo;
-
-    for (uint32_t it = 0; it < ENC_TILE_CHUNKS / BLOCK; ++it) {
-        const uint64_t c0 = t0 + 16ull * (it * BLOCK + threadIdx.x);          // lead-shifted start of the chunk
-        if (c0 >= (uint64_t)total + lead) break;
-        const uint32_t x0 = (uint32_t)(c0 > lead ? c0 - lead : 0);
-        const uint64_t c1 = c0 + 16 - lead;
-        const uint32_t x1 = (uint32_t)(c1 < total ? c1 : total);              // the chunk's positions [x0, x1)
-        const bool whole = x1 - x0 == 16;                                      // then out + x0 is 16-B aligned
-        uint32_t j = jlo, fend = 0;                                            // the frame at hand ends at fend
-        RspFrame f;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        uint32_t x = x0;
-        while (x < x1) {
-            if (x >= fend) {                                                   // zero-length frames are stepped over
-                j = enc_find(so, jlo, j, jhi, x);
-                fend = so[j + 1 - jlo];
-                rsp_frame(a, j, so[j - jlo], f);
-            }
-            const uint32_t k = x - x0, room = min(x1, fend) - x;
-            bool same = false;
-            if (whole && k == 0 && room == 16) {
-                const uint64_t s = rsp_addr(f, x, 15, &same);
-                if (same) {                                                    // one run: 16 source bytes at any alignment
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const EncU4 q = *reinterpret_cast<const EncU4*>(s - sh);
-                    if (sh) {
-                        const uint32_t e = *reinterpret_cast<const uint32_t*>(s - sh + 16);
-                        v.x = __builtin_amdgcn_alignbyte(q.y, q.x, sh);
-                        v.y = __builtin_amdgcn_alignbyte(q.z, q.y, sh);
-                        v.z = __builtin_amdgcn_alignbyte(q.w, q.z, sh);
-                        v.w = __builtin_amdgcn_alignbyte(e, q.w, sh);
-                    } else {
-                        v = make_uint4(q.x, q.y, q.z, q.w);
-                    }
-                    x += 16;
-                    continue;
-                }
-            }
-            if (whole && (k & 3u) == 0 && room >= 4) {
-                const uint64_t s = rsp_addr(f, x, 3, &same);
-                if (same) {                                                    // a dword inside one run
-                    const uint32_t sh = (uint32_t)(s & 3u);
-                    const uint32_t* p = reinterpret_cast<const uint32_t*>(s - sh);
-                    uint32_t d = p[0];
-                    if (sh) d = __builtin_amdgcn_alignbyte(p[1], d, sh);
-                    rsp_put(v, k >> 2, d);
-                    x += 4;
-                    continue;
-                }
-            }
-            const uint32_t b = *reinterpret_cast<const uint8_t*>(rsp_addr(f, x, 0, &same));
-            if (whole) {
-                const uint32_t wd = k >> 2, old = wd == 0 ? v.x : wd == 1 ? v.y : wd == 2 ? v.z : v.w;
-                rsp_put(v, wd, old | (b << (8 * (k & 3u))));
-            } else {
-                out[x] = (uint8_t)b;                                           // the first or last chunk of the output
-            }
-            x += 1;
-        }
-        if (whole) *reinterpret_cast<uint4*>(out + x0) = v;
-    }
-}
+};
 
 }  // namespace gd
+

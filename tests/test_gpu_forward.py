@@ -211,6 +211,39 @@ def test_large_body_straddles_tiles(eng, cfg):
         assert np.isin(want[2], OK).all() and len(want[0]) > 100000 + TILE
 
 
+def test_tile_edges(eng, cfg):
+    """An output of exactly one 16-KiB tile and of one tile plus one byte; a frame edge and a body's first byte (a
+    run edge inside a frame: the written TargetSilo ends there) on the tile boundary."""
+    rng = np.random.default_rng(37)
+    n = 40
+
+    def frames(lens):
+        return [H.encode_frame(dict(BASE, correlation_id=k), bytes(rng.integers(0, 256, size=lens[k], dtype=np.uint8)))
+                for k in range(n)]
+
+    empty = _plain(cfg, frames([0] * n), rng)
+    w0 = F.forward_batch(*empty, None, F.MAX_FC, F.LOCAL_SILO, cfg)
+    flen = int(w0[1][1])                                              # every forwarded frame has the same length
+    assert (w0[2] == F.ST_OK_ADDRESSED).all() and len(w0[0]) == n * flen < TILE
+    for total, split in ((TILE, 0), (TILE + 1, 0), (None, 1), (None, 2)):
+        lens = [0] * n
+        if split == 0:
+            lens[5] = total - n * flen                                # one body brings the total to `total`
+        elif split == 1:
+            lens[5], lens[30] = TILE - 20 * flen, 40                  # frame 20 starts on the tile boundary
+        else:
+            lens[5], lens[20] = TILE - 21 * flen, 40                  # frame 20's body starts on the tile boundary
+        total = n * flen + sum(lens)
+        b = F.pack_frames(frames(lens), b"") + empty[2:]
+        for lead in (0, 9):
+            want = _check(eng, cfg, b, lead=lead)
+            assert len(want[0]) == total
+            if split == 1:
+                assert int(want[1][20]) == TILE
+            if split == 2:
+                assert int(want[1][21]) - lens[20] == TILE
+
+
 def test_more_frame_starts_in_a_tile_than_the_lds_offsets(eng, cfg):
     rng = np.random.default_rng(35)
     frames = [H.encode_frame(dict(BASE, correlation_id=k), b"") for k in range(1502)]

@@ -157,6 +157,36 @@ def test_large_body_straddles_tiles(eng):
         assert (want[2] == R.ST_OK).all() and len(want[0]) > 300000 + TILE    # the body alone spans 18 tiles
 
 
+def test_tile_edges(eng):
+    """An output of exactly one 16-KiB tile and of one tile plus one byte; a frame edge and a body's first byte (a
+    run edge inside a frame) on the tile boundary."""
+    rng = np.random.default_rng(24)
+    frames = [H.encode_frame(dict(BASE, correlation_id=k), b"") for k in range(40)]
+    n = len(frames)
+    empty = _plain(frames)
+    w0 = R.respond_batch(*empty, None, R.INFOS)
+    flen = int(w0[1][1])                                              # every answer has the same length
+    assert (w0[2] == R.ST_OK).all() and len(w0[0]) == n * flen < TILE
+    for total, split in ((TILE, 0), (TILE + 1, 0), (None, 1), (None, 2)):
+        lens = [0] * n
+        if split == 0:
+            lens[5] = total - n * flen                                # one body brings the total to `total`
+        elif split == 1:
+            lens[5], lens[30] = TILE - 20 * flen, 40                  # frame 20 starts on the tile boundary
+        else:
+            lens[5], lens[20] = TILE - 21 * flen, 40                  # frame 20's body starts on the tile boundary
+        total = n * flen + sum(lens)
+        bodies = [bytes(rng.integers(0, 256, size=k, dtype=np.uint8)) for k in lens]
+        b = empty[:6] + (b"".join(bodies), np.concatenate([[0], np.cumsum(lens)]).astype(np.uint64))
+        for lead in (0, 9):
+            want = _check(eng, b, lead=lead)
+            assert len(want[0]) == total
+            if split == 1:
+                assert int(want[1][20]) == TILE
+            if split == 2:
+                assert int(want[1][21]) - lens[20] == TILE
+
+
 def test_skipped_run_longer_than_the_lds_offsets(eng):
     frames = [H.encode_frame(dict(BASE, correlation_id=k), b"") for k in range(1502)]
     batch = list(_plain(frames, bodies=[b"b" * (k % 5) for k in range(1502)]))
